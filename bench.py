@@ -11,6 +11,14 @@ step's per-case outputs (std, PSD, iteration counts) are gathered to rank 0 over
 stream while the next step solves (the final response-spectrum gather of north_star), and
 the line also reports the same steps without the gather.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline figure needs and
+nothing else: it sets up (model, batch, CLOCK_RAMP_S of untimed steps that bring the GPU to its
+steady-state clock), runs W untimed steps, times K pipelined steps (`value`, `ms_per_step`) and
+prints the line.  `--full` adds everything else to the same line: the CPU baseline legs, the
+C3 (QTF), C4 and C5 legs, the serial pass of the same K steps with its kernel times and roofline,
+the bit-for-bit check of the pipelined against the serial outputs and, on N > 1 GPUs, the steps
+without the gather.  `--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -25,6 +33,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "raft-teststuff_amd"))
 
 NCASE = 512
+CLOCK_RAMP_S = 0.5    # untimed steps of a plain run before its warmup: the GPU reaches its steady-state clock
 C5_CHUNKS = 5         # C5 design blocks of a whole sweep: block k+1 is prepared on the host while block k solves
 
 
@@ -276,7 +285,13 @@ def qtf_calibration():
     return float(d["mean_ratio"]), "tools/calibrate_cpu.py --qtf, " + os.path.relpath(QTF_CALIBRATION, ROOT)
 
 
-CPU_BASELINE_CACHE = os.path.join("/tmp", "raft_bench_cpu_baseline.json")
+def _cpu_baseline_cache():
+    """One file per user in the temporary directory: another user's file there cannot be rewritten."""
+    import tempfile
+    return os.path.join(tempfile.gettempdir(), f"raft_bench_cpu_baseline_{os.getuid()}.json")
+
+
+CPU_BASELINE_CACHE = _cpu_baseline_cache()
 
 
 def cpu_baseline_key():
@@ -329,6 +344,29 @@ def pack_outputs(res):
     n = res["std"].shape[0]
     return torch.cat([res["std"].reshape(n, -1), res["psd"].reshape(n, -1),
                       res["iters"].to(torch.float64).reshape(n, 1)], 1)
+
+
+DUMP_ARRAY_BYTES = 16 * 10 ** 6     # per dumped array; the six arrays of a step then stay under 64 MB in all
+DUMP_SEED = 20241016
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: every tensor of a step's BatchResult (what a caller of solve_batch
+    receives) as out_dir/<key>.npy in float64 -- integer outputs converted (exact), complex ones
+    with a trailing axis of 2 (real, imaginary).  An array above DUMP_ARRAY_BYTES keeps a fixed
+    sample of its cases (leading axis): the same sorted, seeded draw for every run with the same
+    --ncase, so two builds write the same cases."""
+    os.makedirs(out_dir, exist_ok=True)
+    for key in sorted(res):
+        a = res[key].cpu().numpy()
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a).view(np.float64).reshape(a.shape + (2,))
+        a = a.astype(np.float64, copy=False)
+        per_case = max(1, a.nbytes // max(1, a.shape[0]))
+        keep = DUMP_ARRAY_BYTES // per_case
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], max(1, keep), replace=False))]
+        np.save(os.path.join(out_dir, key + ".npy"), np.ascontiguousarray(a))
 
 
 def qtf_flops_per_pair(nsub, nkay, nwl):
@@ -746,7 +784,7 @@ def relaunch(nproc, argv):
     before this process touches the GPU, and return its exit code."""
     import socket
     import subprocess
-    if "--no-cpu-baseline" not in argv:
+    if "--full" in argv and "--no-cpu-baseline" not in argv:
         cpu_baselines_cached(harness="--harness-check" in argv)   # this process never touches the GPU: fresh
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -763,7 +801,7 @@ def harness_check(args, world, rank):
     import torch
     import torch.distributed as dist
     base = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         base = cpu_baselines_cached(harness=True, reuse=world > 1)
     if world > 1:
         dist.init_process_group("gloo")
@@ -812,7 +850,14 @@ def main():
     ap.add_argument("--no-c5", action="store_true")
     ap.add_argument("--no-c4", action="store_true")
     ap.add_argument("--harness-check", action="store_true", help="multi-rank harness only (gloo, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the QTF / C4 / C5 legs, the serial pass with the roofline and "
+                         "the output checks (the --no-* options pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch(args.gpus, sys.argv[1:]))       # N ranks, one per GPU
@@ -824,7 +869,7 @@ def main():
     if args.harness_check:
         return harness_check(args, world, rank)
     baselines = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         baselines = cpu_baselines_cached(reuse=world > 1)   # before this process initialises the GPU
     pool, nproc = None, 1     # C5 prepares designs on native host threads (no worker pool)
     import torch
@@ -895,12 +940,23 @@ def main():
     # warmup steps alone start the C2 timing below its steady-state clock (round 3: 0.938 vs
     # 0.869 ms per step with 3 vs 200 warmup steps).  The C2 protocol itself is unchanged.
     legs = {}
-    if not args.no_qtf:
+    if args.full and not args.no_qtf:
         legs["qtf"] = bench_qtf(device, max(20, args.steps // 4), 10, world, rank, dist)
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         legs["c4"] = bench_c4(device, max(3, args.steps // 2), world, rank, dist)
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         legs["c5"] = bench_c5(device, max(3, args.steps // 4), world, rank, dist, pool, nproc)
+    ramp_steps = 0
+    if not args.full:
+        # A plain run has no other leg in front of its steps: CLOCK_RAMP_S of untimed steps stand in
+        # for them (part of the set-up, whatever --warmup says), so that `value` stays the
+        # steady-state-clock figure it has always been, also with a handful of warmup steps.
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < CLOCK_RAMP_S:
+            for _ in range(20):
+                step(None, ramp_steps % nstream)
+                ramp_steps += 1
+            torch.cuda.synchronize()
     for i in range(args.warmup):
         res = step(None, i % nstream)
         if world > 1:
@@ -952,23 +1008,25 @@ def main():
                 assert out.shape[0] == world * args.ncase and torch.all(out[:, -1] >= 1)
         return float(t.item()), (ev, end), r, gms
 
-    dt_serial, (ev, end), res, _ = timed(False)
-    dt_ng, _, r_pipe, _ = timed(False, pipelined=True)
-    # the pipelined steps solve the same batch: the same bits as the serial pass
-    assert all(torch.equal(r_pipe[k], res[k]) for k in ("iters", "std", "psd")), "pipelined C2 step differs"
-    dt_max, gather_ms = dt_ng, None
+    dt_ng = gather_ms = None
+    if args.full:
+        dt_serial, (ev, end), res, _ = timed(False)
+        dt_ng, _, r_pipe, _ = timed(False, pipelined=True)
+        # the pipelined steps solve the same batch: the same bits as the serial pass
+        assert all(torch.equal(r_pipe[k], res[k]) for k in ("iters", "std", "psd")), "pipelined C2 step differs"
+        dt_max = dt_ng
+    # the headline pass: K pipelined steps, on N > 1 GPUs with each step's gather
     if world > 1:
-        dt_max, _, _, gather_ms = timed(True, pipelined=True)
-    tab_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
-    nxt = [e[0] for e in ev[1:]] + [end]
-    kern_ms = float(np.mean([e[1].elapsed_time(n) for e, n in zip(ev, nxt)]))
+        dt_max, _, r_pipe, gather_ms = timed(True, pipelined=True)
+    elif not args.full:
+        dt_max, _, r_pipe, _ = timed(False, pipelined=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r_pipe, args.dump_outputs)      # the last timed step of the headline pass
 
-    iters = res["iters"].cpu().numpy()
-    status = res["status"].cpu().numpy()
+    iters = r_pipe["iters"].cpu().numpy()
+    status = r_pipe["status"].cpu().numpy()
     circ = dd.node[N_CIRC()].cpu().numpy() if dd.nn else np.zeros(0)
     nc, nr = int((circ != 0).sum()), int((circ == 0).sum())
-    flops = float(sum(flops_per_case(int(n), dd.nw, nc, nr, dd.nn) for n in iters))
-    achieved = flops / (kern_ms * 1e-3)
 
     total_cases = args.ncase * world * args.steps
     line = {
@@ -990,28 +1048,38 @@ def main():
                    "nodes_circ_rect": [nc, nr], "nIter": int(m.nIter), "headings": len(dd.headings),
                    "parallelism": f"case-sharded x{world}",
                    "pipeline": f"consecutive steps rotate over {nstream} HIP streams with their own wave "
-                               "tables and outputs (value, ms_per_step); kernel_ms and the roofline from a "
-                               "serial pass of the same K steps on one stream",
-                   "ms_per_step_serial": dt_serial / args.steps * 1e3},
-        "roofline": {"bound": "valu", "achieved": achieved / 1e12, "peak": PEAK_FP64 / 1e12, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_FP64, "traffic": pmc_traffic("solve", *solve_kernels(dd.nw)),
-                     **hw_util("solve", solve_kernels(dd.nw), kern_ms),
-                     "l2": pmc_l2(solve_kernel_name(dd.nw), kern_ms),
-                     "kernel": solve_kernel_name(dd.nw), "kernels_timed": list(solve_kernels(dd.nw)),
-                     "kernel_ms": kern_ms,
-                     "wave_tables_ms": tab_ms,
-                     "flops_per_launch": flops,
-                     "note": "FP64 VALU bound (no MFMA, DESIGN.md §4; peak = MI355X FP64 vector rate); algorithmic "
-                             "FLOPs from SURVEY.md §8(d) over the solve call's launches (kernels_timed, HIP events on "
-                             "their stream); traffic = HBM bytes of those launches from "
-                             + os.path.relpath(PMC_SUMMARY, ROOT)},
+                               "tables and outputs (value, ms_per_step); with --full, kernel_ms and the roofline "
+                               "from a serial pass of the same K steps on one stream"},
         "iterations_mean": float(iters.mean()),
         "converged_frac": float((status == 1).mean()),
     }
+    if not args.full:
+        line["config"]["clock_ramp_steps"] = ramp_steps     # untimed, before the warmup steps
+    if args.full:
+        tab_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+        nxt = [e[0] for e in ev[1:]] + [end]
+        kern_ms = float(np.mean([e[1].elapsed_time(n) for e, n in zip(ev, nxt)]))
+        flops = float(sum(flops_per_case(int(n), dd.nw, nc, nr, dd.nn) for n in iters))
+        achieved = flops / (kern_ms * 1e-3)
+        line["config"]["ms_per_step_serial"] = dt_serial / args.steps * 1e3
+        line["roofline"] = {
+            "bound": "valu", "achieved": achieved / 1e12, "peak": PEAK_FP64 / 1e12, "unit": "TFLOP/s",
+            "frac": achieved / PEAK_FP64, "traffic": pmc_traffic("solve", *solve_kernels(dd.nw)),
+            **hw_util("solve", solve_kernels(dd.nw), kern_ms),
+            "l2": pmc_l2(solve_kernel_name(dd.nw), kern_ms),
+            "kernel": solve_kernel_name(dd.nw), "kernels_timed": list(solve_kernels(dd.nw)),
+            "kernel_ms": kern_ms,
+            "wave_tables_ms": tab_ms,
+            "flops_per_launch": flops,
+            "note": "FP64 VALU bound (no MFMA, DESIGN.md §4; peak = MI355X FP64 vector rate); algorithmic "
+                    "FLOPs from SURVEY.md §8(d) over the solve call's launches (kernels_timed, HIP events on "
+                    "their stream); traffic = HBM bytes of those launches from "
+                    + os.path.relpath(PMC_SUMMARY, ROOT)}
     if world > 1:
         n_out = args.ncase * (6 + 6 * dd.nw + 1) * 8
-        line["gather"] = {"included_in_value": True, "value_without_gather": total_cases / dt_ng,
-                          "ms_per_step_without_gather": dt_ng / args.steps * 1e3,
+        without = {"value_without_gather": total_cases / dt_ng,
+                   "ms_per_step_without_gather": dt_ng / args.steps * 1e3} if args.full else {}
+        line["gather"] = {"included_in_value": True, **without,
                           "last_gather_ms": gather_ms, "bytes_per_rank_per_step": n_out,
                           "bytes_into_rank0_per_step": (world - 1) * n_out,
                           "note": "per step: gather (RCCL) of every rank's std, PSD and iteration counts to rank 0 on a "

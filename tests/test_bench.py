@@ -21,7 +21,7 @@ def _run(*argv):
 
 
 def test_gpus2_launches_two_ranks_one_line():
-    lines = _run("--gpus", "2", "--harness-check", "--steps", "3", "--warmup", "1")
+    lines = _run("--gpus", "2", "--harness-check", "--full", "--steps", "3", "--warmup", "1")
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["steps"] == 3
@@ -36,6 +36,40 @@ def test_gpus2_launches_two_ranks_one_line():
 def test_gpus1_single_rank():
     lines = _run("--gpus", "1", "--harness-check", "--steps", "2", "--warmup", "0")
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 1
+    # a plain run (no --full) times its steps only: no CPU baseline leg
+    d = json.loads(lines[0])
+    assert "cpu_baseline" not in d and d["steps"] == 2 and d["ms_per_step"] >= 1.0
+
+
+def test_dump_outputs_fixed_sample(tmp_path):
+    """--dump-outputs: every output as float64 <name>.npy, complex ones with a trailing (re, im)
+    axis, integer ones converted; an array above DUMP_ARRAY_BYTES keeps the same seeded sample
+    of its cases in every run, whole cases, in ascending order."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, nw = 40, 1000
+    rng = np.random.default_rng(1)
+    Xi = rng.standard_normal((n, 6, nw)) + 1j * rng.standard_normal((n, 6, nw))
+    res = {"Xi": torch.tensor(Xi), "iters": torch.arange(n, dtype=torch.int32),
+           "std": torch.tensor(rng.standard_normal((n, 6)))}
+    cap = 10 * 6 * nw * 16 + 5       # room for 10 whole cases of Xi
+    old, bench.DUMP_ARRAY_BYTES = bench.DUMP_ARRAY_BYTES, cap
+    try:
+        bench.dump_outputs(res, str(tmp_path / "a"))
+        bench.dump_outputs(res, str(tmp_path / "b"))
+    finally:
+        bench.DUMP_ARRAY_BYTES = old
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in res}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["Xi"].shape == (10, 6, nw, 2) and a["Xi"].nbytes <= cap
+    assert np.array_equal(a["iters"], np.arange(n)) and np.array_equal(a["std"], res["std"].numpy())
+    # the kept cases: distinct rows of the input, ascending, the same in both dumps
+    rows = [int(np.flatnonzero((Xi.real[:, 0, 0] == x))[0]) for x in a["Xi"][:, 0, 0, 0]]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(a["Xi"][..., 0], Xi.real[rows]) and np.array_equal(a["Xi"][..., 1], Xi.imag[rows])
+    assert np.array_equal(a["Xi"], np.load(tmp_path / "b" / "Xi.npy"))
 
 
 def test_host_cores_respects_affinity():
