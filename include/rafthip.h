@@ -458,6 +458,12 @@ int rh_qtf_slender(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double* w,
 int rh_qtf_slender_ext(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double* w, const rh_c128* Xi0,
                        const double* M66, rh_c128* qtf, void* work, long long work_bytes, int flags, rh_stream stream);
 
+/* Which path a QTF call with q takes on ctx as it is set now: 1 = the MFMA path (q->order == 1
+ * and rh_set_qtf_path(ctx, 0)), whose whole-QTF calls leave the incident-wave parts in `work`
+ * for RH_QTF_INCIDENT_CACHED; 0 = the per-pair kernel, which fills none of them.  RH_EINVAL for
+ * a null argument.  A caller that keeps a workspace asks this before it vouches for the cache. */
+int rh_qtf_keeps_incident(rh_ctx* ctx, const rh_qtf_design* q);
+
 /* The upper-triangle pairs (w1 <= w2) of one rank of a QTF sharded over nrank devices, no
    Hermitian fill.  The upper triangle is cut into 16 x 16 pair tiles (i1 tile T1 <= i2 tile T2,
    n2 rounded up to 16), numbered row-major; rank r owns the tiles t with t % nrank == r

@@ -980,6 +980,11 @@ int rh_qtf_slender_ext(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double
   return qtf_launch(ctx, q, nw, w, Xi0, M66, 0, 1, 1, qtf, work, work_bytes, stream, "rh_qtf_slender_ext", flags);
 }
 
+int rh_qtf_keeps_incident(rh_ctx* ctx, const rh_qtf_design* q) {
+  if (!ctx || !q) return fail(RH_EINVAL, "rh_qtf_keeps_incident: null argument");
+  return q->order == 1 && !ctx->qtf_direct ? 1 : 0;   // `gemm` of qtf_launch
+}
+
 int rh_qtf_slender_rows(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double* w, const rh_c128* Xi0,
                         const double* M66, int rank, int nrank, rh_c128* qtf, void* work, long long work_bytes,
                         rh_stream stream) {

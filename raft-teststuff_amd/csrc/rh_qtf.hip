@@ -885,7 +885,20 @@ __global__ __launch_bounds__(kQtfTile * NWV) RH_QTF_ATTR void k_qtf_pairs(rh_qtf
       for (int d = 0; d < 6; ++d) Q[d] = add(Q[d], mk(r[(2 * d) * kQtfTile + lane], r[(2 * d + 1) * kQtfTile + lane]));
     }
   }
-  if (!active) return;
+  if (!active) {
+    // w2 < w1 on an unsorted grid: the reference skips the pair and keeps the zeros of its
+    // np.zeros (:1442, :1517-1518), so the entry and its mirror are zero, not left unwritten
+    if (i2 < n2) {
+      rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6;
+      rh_c128* lo = qtf + ((size_t)i2 * n2 + i1) * 6;
+#pragma unroll
+      for (int d = 0; d < 6; ++d) {
+        st(up + d, mk(0, 0));
+        if (mirror) st(lo + d, mk(0, 0));
+      }
+    }
+    return;
+  }
   // Hermitian fill (:1639-1640): qtf + conj(qtf).T - diag(conj(diag(qtf)))
   rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6;
   if (!mirror) {

@@ -119,6 +119,7 @@ def lib():
                                        ctypes.c_longlong, ctypes.c_int, _p],
                 "rh_qtf_slender_rows": [_p, ctypes.POINTER(RhQtfDesign), ctypes.c_int, _p, _p, _p, ctypes.c_int,
                                         ctypes.c_int, _p, _p, ctypes.c_longlong, _p],
+                "rh_qtf_keeps_incident": [_p, ctypes.POINTER(RhQtfDesign)],
                 "rh_qtf_hermitian_fill": [_p, ctypes.c_int, _p, _p],
                 "rh_set_solver": [_p, ctypes.c_int],
                 "rh_set_a0": [_p, ctypes.c_int],

@@ -272,7 +272,10 @@ class QtfDevice:
                                            N.RH_QTF_INCIDENT_CACHED if incident_cached else 0,
                                            N.stream_handle(torch, self.dev)),
                 "rh_qtf_slender_ext")
-        self._incident_ready = True
+        # only a call on the MFMA path (order == 1, the context's default path) leaves the
+        # incident-wave parts in the workspace; the per-pair kernel fills none of them
+        self._incident_ready = N.lib().rh_qtf_keeps_incident(N.context(self.dev_index),
+                                                             ctypes.byref(self.struct_)) == 1
         if on_computed is not None:
             on_computed()
         return out

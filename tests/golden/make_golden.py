@@ -392,6 +392,118 @@ def golden_qtf():
     print("wrote c3_qtf.npz", file=sys.stderr)
 
 
+def rect_variant(design):
+    """Design B of golden_qtf_rect: VolturnUS-S_example with rectangular, tapered, inclined,
+    twisted surface-piercing outer columns (Ca_p1 != Ca_p2, CaEnd != 0, MCF asked for and
+    dropped by Member because they are not circular), three-station pontoons (taper, Ca per
+    station, CaEnd != 0) and a MacCamy-Fuchs centre column (Kim & Yue rows beside them)."""
+    d = json.loads(json.dumps(design, default=str))
+    edits = {
+        "outer_column": dict(shape="rect", rB=[56.75, 3.0, 15], gamma=25.0, stations=[0, 20, 35],
+                             d=[[12.5, 10.0], [12.5, 10.0], [9.0, 7.0]], Ca=[[0.93, 0.5], [0.8, 0.4], [0.6, 0.9]],
+                             CaEnd=[0.7, 0.5, 0.3], MCF=True),
+        "pontoon": dict(stations=[0, 20, 40.5], d=[[12.4, 7.0], [10.0, 6.0], [12.4, 7.0]],
+                        Ca=[[2.2, 0.2], [1.8, 0.5], [2.2, 0.2]], Cd=[[1.5, 2.2]] * 3, CaEnd=0.4),
+        "center_column": dict(MCF=True),
+    }
+    for m in d["platform"]["members"]:
+        e = edits.get(m["name"])
+        if e is None:
+            continue
+        if m["name"] != "center_column":
+            for k in [k for k in m if k.startswith("cap_") or k in ("l_fill", "rho_fill")]:
+                m.pop(k)
+        m.update(e)
+    return d
+
+
+SEC_PLATFORM = dict(potSecOrder=1, min_freq2nd=0.04, max_freq2nd=0.25, df_freq2nd=0.014)   # n2 = 17
+
+
+def golden_qtf_rect():
+    """The slender-body QTF on rectangular and mixed-Ca members (raft/raft_fowt.py:1534-1535,
+    :1561-1575, :1584, :1615-1627), which OC4semi never enters: calcQTF_slenderBody of
+    VolturnUS-S_example (design A: rectangular submerged pontoons with Ca [2.2, 0.2], no
+    MacCamy-Fuchs member) and of rect_variant (design B) on a 24-frequency grid that runs
+    past the first-order grid (zero fill of the RAO, :1417), with a seeded RAO moving in all
+    six DOFs at 0 and 30 degrees and with the fixed body at 30 degrees; and one potSecOrder=1
+    solve of design A (Hs = 2 m: Hs = 6 m does not converge within the design's nIter = 4 and
+    forms no QTF).  Writes qtf_rect.npz and designs/VolturnUS-S_rectcols.json."""
+    import raft.raft_fowt as rf
+    rf.interp2d = bilinear_interp2d
+    base = load_design(os.path.join(REF, "examples", "VolturnUS-S_example.yaml"))
+    with open(os.path.join(HERE, "designs", "VolturnUS-S_example.json")) as f:
+        exported = json.load(f)
+    with open(os.path.join(HERE, "designs", "VolturnUS-S_rectcols.json"), "w") as f:
+        json.dump(rect_variant(exported), f, indent=1, default=str)
+    case0 = dict(zip(base["cases"]["keys"], base["cases"]["data"][0]))
+    case0["wind_speed"] = 0
+    out = {}
+    w2 = np.linspace(0.25, 1.6, 24)
+    rng = np.random.default_rng(7)
+    X = None
+    for tag, design in (("A", base), ("B", rect_variant(base))):
+        model = raft.Model(json.loads(json.dumps(design, default=str)))
+        fowt = model.fowtList[0]
+        prepare_fowt(fowt, dict(case0))
+        T = design_tables(fowt)
+        mcf = T.pop("node_Imat_MCF", None)
+        if mcf is not None:                      # keep a sample of bins only (fixture size)
+            T["node_Imat_MCF_bins"] = np.arange(0, fowt.nw, 37)
+            T["node_Imat_MCF_sample"] = mcf[..., ::37]
+        out.update({f"{tag}_{k}": v for k, v in T.items()})
+        if X is None:
+            X = (rng.normal(size=(6, fowt.nw)) + 1j * rng.normal(size=(6, fowt.nw))) * \
+                np.array([1, 1, 1, .02, .02, .02])[:, None]
+            assert np.sum(w2 > fowt.w[-1]) >= 3                       # entries past the first-order grid
+        fowt.w1_2nd = w2.copy()
+        fowt.w2_2nd = w2.copy()
+        fowt.k1_2nd = np.array([raft.helpers.waveNumber(w, fowt.depth) for w in w2])
+        fowt.k2_2nd = fowt.k1_2nd.copy()
+        fowt.outFolderQTF = None
+        out["qtf_k"] = fowt.k1_2nd.copy()
+        for key, bdeg, Xi0 in (("b0", 0.0, X), ("b30", 30.0, X), ("b30_fixed", 30.0, None)):
+            fowt.beta = np.array([np.deg2rad(bdeg)])
+            t0 = time.perf_counter()
+            fowt.calcQTF_slenderBody(0, Xi0=Xi0, verbose=False)
+            out[f"{tag}_qtf_{key}"] = fowt.qtf.copy()
+            print(f"  qtf_rect: design {tag} {key} {time.perf_counter() - t0:.1f}s", file=sys.stderr)
+    out.update(qtf_w=w2, qtf_X=X, qtf_betas=np.deg2rad([0.0, 30.0, 30.0]))
+    # potSecOrder=1 solve of design A
+    design = json.loads(json.dumps(base, default=str))
+    design["platform"].update(SEC_PLATFORM)
+    design["platform"].pop("outFolderQTF", None)
+    model = raft.Model(design)
+    fowt = model.fowtList[0]
+    case = dict(case0, wave_heading=30, wave_height=2.0)
+    prepare_fowt(fowt, dict(case))
+    T = design_tables(fowt)
+    for k, v in T.items():                       # the same body as design A above
+        assert np.array_equal(v, out["A_" + k]), k
+    captured = {}
+    orig = fowt.calcQTF_slenderBody
+
+    def spy(waveHeadInd, Xi0=None, verbose=False, iCase=None, iWT=None):
+        captured["Xi0"] = np.array(Xi0)
+        return orig(waveHeadInd, Xi0=Xi0, verbose=False, iCase=iCase, iWT=iWT)
+    fowt.calcQTF_slenderBody = spy
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        Xi = model.solveDynamics(dict(case), display=2)
+    its = [int(m) + 1 for m in re.findall(r"Iteration (\d+), converged", buf.getvalue())]
+    assert len(its) == 2, its
+    out.update(out_Xi=np.array(Xi), out_iters_pair=np.array(its), out_Xi0=captured["Xi0"], out_qtf=fowt.qtf.copy(),
+               out_Fhydro_2nd=fowt.Fhydro_2nd.copy(), out_Fhydro_2nd_mean=fowt.Fhydro_2nd_mean.copy(),
+               out_zeta=fowt.zeta.copy(), out_S=fowt.S.copy(), out_B_drag=fowt.B_hydro_drag.copy(),
+               w1_2nd=fowt.w1_2nd.copy(), k1_2nd=fowt.k1_2nd.copy(), nIter=np.int64(model.nIter),
+               XiStart=np.float64(model.XiStart), sec_platform_json=np.array(json.dumps(SEC_PLATFORM)),
+               cases_json=np.array(json.dumps([{k: np.atleast_1d(case[k]).tolist() for k in
+                                               ["wave_spectrum", "wave_period", "wave_height", "wave_heading"]}])))
+    print(f"  qtf_rect: solve iters {its}, n2={len(fowt.w1_2nd)}", file=sys.stderr)
+    np.savez_compressed(os.path.join(HERE, "qtf_rect.npz"), **out)
+    print("wrote qtf_rect.npz", file=sys.stderr)
+
+
 # Stand-in array-level (shared-line) stiffness for the 2-FOWT farm: both bodies anchored
 # by C_MOOR at the FOWT level plus a shared surge/sway line between them.
 K_SHARED = np.diag([3.0e4, 1.0e4, 0.0, 0.0, 0.0, 0.0])
@@ -649,6 +761,8 @@ def main(which):
         golden_qtf12d()
     if "qtf" in which:
         golden_qtf()
+    if "qtf_rect" in which:
+        golden_qtf_rect()
     if "farm" in which:
         golden_farm()
     if "sweep" in which:

@@ -51,6 +51,7 @@ def test_library_loads_and_binds(libpath):
     assert L.rh_set_solver(None, 0) == N.RH_EINVAL
     assert L.rh_set_qtf_waves(None, 4) == N.RH_EINVAL
     assert b"null context" in L.rh_last_error()
+    assert L.rh_qtf_keeps_incident(None, None) == N.RH_EINVAL
     for f in declared_functions():
         assert hasattr(L, f)
 

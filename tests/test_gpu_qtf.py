@@ -396,13 +396,134 @@ def test_incident_cached_qtf_equals_full_qtf(T):
         N.check(N.lib().rh_set_qtf_path(ctx, 0), "rh_set_qtf_path")
 
 
+def _cache_setup(T):
+    """OC4semi on the golden 42-frequency grid: (fowt, design, M66, two RAOs, a QtfDevice maker).
+    A new QtfDevice's workspace is filled with NaN: it is uninitialised memory, and a block the
+    allocator hands back from an earlier QtfDevice of the same grid would hold a valid cache."""
+    import torch
+    from raft.qtf import QtfDevice
+    m, f = make(T)
+    dd = f.device_design()
+    M66 = torch.tensor(f.M_struc, dtype=torch.float64, device=dd.device).contiguous()
+    X1 = torch.tensor(T["out_Xi0"], dtype=torch.complex128, device=dd.device)
+    rng = np.random.default_rng(31)
+    X2 = torch.tensor((rng.normal(size=X1.shape) + 1j * rng.normal(size=X1.shape)) * np.abs(T["out_Xi0"]).max(),
+                      dtype=torch.complex128, device=dd.device)
+
+    def new(w2=T["w1_2nd"], k2=T["k1_2nd"]):
+        qd = QtfDevice(f, w2, k2, 0.0, 0)
+        qd.work.fill_(float("nan"))
+        return qd
+    return m, f, dd, M66, X1, X2, new
+
+
+def _per_pair(fn):
+    from raft import _native as N
+    ctx = N.context(0)
+    N.check(N.lib().rh_set_qtf_path(ctx, 1), "rh_set_qtf_path")
+    try:
+        return fn()
+    finally:
+        N.check(N.lib().rh_set_qtf_path(ctx, 0), "rh_set_qtf_path")
+
+
+def test_incident_cache_is_not_claimed_after_a_per_pair_call(T):
+    """A whole QTF on the per-pair path fills none of the MFMA path's incident-wave parts: a
+    later incident_cached call on that QtfDevice is refused (or gives a fresh device's bits),
+    never the contents of a workspace that was not filled."""
+    m, f, dd, M66, X1, X2, new = _cache_setup(T)
+    fresh = new().qtf(dd.w, X2, M66).cpu().numpy()
+    qd = new()
+    _per_pair(lambda: qd.qtf(dd.w, X1, M66))
+    try:
+        got = qd.qtf(dd.w, X2, M66, incident_cached=True).cpu().numpy()
+    except ValueError as e:
+        assert "earlier whole-QTF call" in str(e)
+    else:
+        np.testing.assert_array_equal(got, fresh)
+    # and a whole MFMA call makes the cache valid again
+    qd.qtf(dd.w, X1, M66)
+    np.testing.assert_array_equal(qd.qtf(dd.w, X2, M66, incident_cached=True).cpu().numpy(), fresh)
+
+
+def test_unsorted_grid_takes_whole_calls_one_after_another(T):
+    """order == 0 (two frequencies swapped): the per-pair kernel is the only path, so a second
+    call made the way second_order._second_pass makes it (incident_cached = the device's
+    _incident_ready) is a whole call again and gives a fresh device's bits.  The pair the
+    reference skips (w2 < w1 at i2 > i1, raft/raft_fowt.py:1517-1518) and its mirror are zero,
+    as in the reference's np.zeros, whatever the output buffer held, and the whole QTF agrees
+    with the oracle on that grid (1e-9 normwise and of the largest entry)."""
+    import torch
+    from oracle import qtf_oracle as Q
+    m, f, dd, M66, X1, X2, new = _cache_setup(T)
+    w2, k2 = T["w1_2nd"].copy(), T["k1_2nd"].copy()
+    w2[[5, 6]], k2[[5, 6]] = w2[[6, 5]], k2[[6, 5]]
+    qd = new(w2, k2)
+    assert qd.order == 0
+    a1 = qd.qtf(dd.w, X1, M66, incident_cached=getattr(qd, "_incident_ready", False)).cpu().numpy()
+    a2 = qd.qtf(dd.w, X2, M66, incident_cached=getattr(qd, "_incident_ready", False)).cpu().numpy()
+    out = torch.full([qd.n2, qd.n2, 6], complex(np.nan, np.nan), dtype=torch.complex128, device=dd.device)
+    a3 = qd.qtf(dd.w, X2, M66, out=out).cpu().numpy()
+    assert not np.any(a3[5, 6]) and not np.any(a3[6, 5]) and np.all(np.isfinite(a3.view(float)))
+    np.testing.assert_array_equal(a3, a2)
+    ref = Q.qtf_slender(T, X2.cpu().numpy(), w2, k2, 0.0)[:, :, 0, :]
+    assert rel(a2, ref) < RTOL, rel(a2, ref)
+    np.testing.assert_allclose(a2, ref, rtol=0, atol=RTOL * np.abs(ref).max())
+    np.testing.assert_array_equal(a1, new(w2, k2).qtf(dd.w, X1, M66).cpu().numpy())
+    np.testing.assert_array_equal(a2, new(w2, k2).qtf(dd.w, X2, M66).cpu().numpy())
+    assert not np.array_equal(a1, a2)
+    with pytest.raises(ValueError):
+        qd.qtf(dd.w, X2, M66, incident_cached=True)
+
+
+def test_incident_cache_survives_a_rank_call_on_the_same_device(T):
+    """A whole MFMA call, then one rank's tiles (rank 1 of 8, another RAO) through the same
+    workspace, then incident_cached: the rank call rewrites the incident-wave parts of its own
+    rows and tiles with the same values (KS is indexed by the global tile), so the cached call
+    still gives a fresh device's bits."""
+    import torch
+    m, f, dd, M66, X1, X2, new = _cache_setup(T)
+    fresh = new().qtf(dd.w, X2, M66).cpu().numpy()
+    qd = new()
+    qd.qtf(dd.w, X1, M66)
+    part = torch.zeros([qd.n2, qd.n2, 6], dtype=torch.complex128, device=dd.device)
+    qd.qtf_rows(dd.w, X1 * 0.7, M66, part, 1, 8)
+    got = qd.qtf(dd.w, X2, M66, incident_cached=True).cpu().numpy()
+    np.testing.assert_array_equal(got, fresh)
+
+
+def test_batch_second_pass_after_a_per_pair_call_on_the_kept_device(T):
+    """A FOWT keeps its QtfDevice per heading.  A per-pair whole call on it (a cross-check, as
+    the tests above make) must not make the next potSecOrder=1 batch read an unfilled cache:
+    the batch's results equal a cold model's."""
+    from raft.hydro_math import DEG2RAD
+    m, f, dd, M66, X1, X2, new = _cache_setup(T)
+    gold = _case(T)
+    cases = [dict(gold), dict(gold, wave_height=4.0, wave_period=10.0)]
+    qd = f._qtf_device(float(gold["wave_heading"]) * DEG2RAD)
+    qd.work.fill_(float("nan"))
+    _per_pair(lambda: qd.qtf(dd.w, X1, M66))
+    r = m.analyzeCasesBatch(cases, want=("psd", "std", "zeta", "B_drag", "Fhydro_2nd"))
+    assert f._qtf_device(float(gold["wave_heading"]) * DEG2RAD) is qd
+    cold, _ = make(T)
+    rc = cold.analyzeCasesBatch(cases, want=("psd", "std", "zeta", "B_drag", "Fhydro_2nd"))
+    assert np.all(rc["iters_pair"][:, 1] > 0)
+    np.testing.assert_array_equal(r["iters_pair"], rc["iters_pair"])
+    for k in ("Xi", "Fhydro_2nd", "f2nd_mean", "B_drag"):
+        np.testing.assert_array_equal(r[k], rc[k], err_msg=k)
+    assert list(r["iters_pair"][0]) == list(T["out_iters_pair"])
+    assert rel(r["Xi"][0], T["out_Xi"][0]) < RTOL
+
+
 @pytest.mark.gpu
 def test_qtf_of_a_design_without_kim_yue_rows_cached_and_oracle():
     """VolturnUS-S (no MacCamy-Fuchs members: no Kim & Yue rows, nkr = 0; rectangular pontoons)
-    on a 24-frequency grid: the native tables equal build_tables, the MFMA QTF agrees with the
-    per-pair kernel (1e-12), and a further RAO with the incident parts kept equals a whole QTF
-    bit for bit.  (No reference run of this design's QTF exists: the QTF itself is pinned on
-    OC4semi above; here the nkr = 0 paths are.)"""
+    on a 24-frequency grid at 20 degrees: the native tables equal build_tables, the MFMA QTF
+    agrees with the per-pair kernel (1e-12) and with the oracle on the reference's node tables
+    of this design (tests/golden/qtf_rect.npz design A; 1e-9 normwise and elementwise to 1e-9 of
+    the largest force / moment entry; the mass matrix is this model's own), and a further RAO
+    with the incident parts kept equals a whole QTF bit for bit.  The reference runs of this
+    design's QTF are in tests/test_gpu_qtf_rect.py."""
     import torch
     import raft
     from raft import _native as N
@@ -439,3 +560,11 @@ def test_qtf_of_a_design_without_kim_yue_rows_cached_and_oracle():
     finally:
         N.check(N.lib().rh_set_qtf_path(ctx, 0), "rh_set_qtf_path")
     assert np.abs(a1).max() > 0 and rel(a1, p1) < 1e-12, rel(a1, p1)
+    from oracle import qtf_oracle as Q
+    TA = {k[2:]: v for k, v in load_golden("qtf_rect").items() if k.startswith("A_")}
+    np.testing.assert_array_equal(TA["w"], f.w)
+    np.testing.assert_array_equal(TA["r6"], f.r6)
+    ref = Q.qtf_slender(dict(TA, M_struc=np.asarray(f.M_struc, dtype=float)), X1, w2, k2, np.deg2rad(20.0))[:, :, 0, :]
+    assert rel(a1, ref) < RTOL, rel(a1, ref)
+    for s in (slice(0, 3), slice(3, 6)):
+        np.testing.assert_allclose(a1[..., s], ref[..., s], rtol=0, atol=RTOL * np.abs(ref[..., s]).max())
