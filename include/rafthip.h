@@ -227,6 +227,46 @@ int rh_wave_tables(rh_ctx* ctx, const rh_design* d, const double* beta,
 int rh_wave_tables_batch(rh_ctx* ctx, const rh_design* designs, int ndesign, const double* beta, int hstride,
                          rh_stream stream);
 
+/* Potential-flow (BEM) wave excitation per unit wave amplitude of a design that brings first-order
+ * coefficient files (potFirstOrder = 1), FOWT.calcHydroExcitation's F_BEM block
+ * (raft/raft_fowt.py:1039-1093) on the device.  Per output heading h and bin b:
+ *   bdeg = (degrees(beta[h]) - heading_adjust_deg) % 360, bracketed in bem_headings_deg with the
+ *   reference's two wrap branches (`<=` the first heading, `>=` the last one), f1 = 1 - f2;
+ *   X' = X_BEM[i1] f1 + X_BEM[i2] f2 (each X_BEM[i] is in its own heading's wave frame);
+ *   rotated to the global frame by beta[h] (surge/sway and roll/pitch pairs);
+ *   fbem[h][:,b] = X * exp(-i k[b] (x_ref cos(beta[h]) + y_ref sin(beta[h])));
+ *   fexc[h][:,b] = finer_in[h][:,b] + fbem[h][:,b].
+ * F_BEM = zeta * fbem; a BEM design's descriptor points `finer` at fexc, so that every solver path
+ * takes its unit-amplitude first-order excitation from one table, while the strip-theory table
+ * finer_in stays what F_hydro_iner is reported from.
+ * k: device [nw].  bem_headings_deg: device [nhb] (deg in [0, 360), ascending for nhb > 1).
+ * X_BEM: device [nhb][6][nw].  beta: device [nh] (rad).  finer_in, fbem_out, fexc_out: device
+ * [nh][6][nw]; fexc_out may not alias finer_in.  One lane per (heading, bin) on `stream`; no
+ * allocation, no host synchronisation. */
+int rh_bem_excitation(rh_ctx* ctx, int nw, const double* k, int nhb, const double* bem_headings_deg,
+                      const rh_c128* X_BEM, int nh, const double* beta, double heading_adjust_deg, double x_ref,
+                      double y_ref, const rh_c128* finer_in, rh_c128* fbem_out, rh_c128* fexc_out, rh_stream stream);
+
+/* One design's arguments of rh_bem_excitation, for the batched form. */
+typedef struct {
+  int nw, nhb, nh, pad_;
+  double heading_adjust_deg, x_ref, y_ref;
+  const double* k;             /* [nw] */
+  const double* headings_deg;  /* [nhb] */
+  const rh_c128* X;            /* [nhb][6][nw] */
+  const double* beta;          /* [nh] rad */
+  const rh_c128* finer;        /* [nh][6][nw] strip-theory table (read) */
+  rh_c128* fbem;               /* [nh][6][nw] (written) */
+  rh_c128* fexc;               /* [nh][6][nw] (written) */
+} rh_bem_design;
+
+/* rh_bem_excitation for many designs in ONE launch (the wave tables of a design batch,
+ * raft/prep.py tabulate_batch).  designs: HOST array of ndesign records, validated here;
+ * designs_dev: the same records in device memory (the caller's upload, read by the kernel).
+ * A record with nhb = 0 is skipped (a design without BEM excitation). */
+int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* designs, const rh_bem_design* designs_dev,
+                            rh_stream stream);
+
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
  * (raft/raft_model.py:877-1013) including FOWT.calcHydroLinearization (raft/raft_fowt.py:

@@ -17,6 +17,7 @@
 #include "rh_device.h"
 
 #include "rh_kernels.hip"   // kernels + their host launchers (this translation unit: default scheduler)
+#include "rh_bem.hip"       // k_bem_excitation: the BEM part of the wave tables (potFirstOrder = 1)
 #include "rh_qtf.hip"
 #include "rh_qtf_mfma.hip"
 #include "rh_solve.hip"        // k_solve_lds: only the two-pass <2, 512, false, 2> is instantiated here
@@ -390,6 +391,52 @@ int rh_wave_tables_batch(rh_ctx* ctx, const rh_design* designs, int ndesign, con
   dim3 grid((nwmax + 63) / 64, nhmax, ndesign);
   hipLaunchKernelGGL(rh::k_wave_tables_batch, grid, dim3(64 * rh::kWtN), 0, s, staged_designs(ctx), beta, hstride);
   return designs_used(ctx, s);
+}
+
+namespace {
+int check_bem_design(const rh_bem_design& d, const char* who) {
+  if (d.nw < 1 || d.nhb < 1 || d.nh < 1) return fail(RH_EINVAL, "%s: nw=%d, nhb=%d, nh=%d must be >= 1", who, d.nw, d.nhb, d.nh);
+  if (!d.k || !d.headings_deg || !d.X || !d.beta || !d.finer || !d.fbem || !d.fexc)
+    return fail(RH_EINVAL, "%s: null argument", who);
+  if (d.fexc == d.finer || d.fbem == d.fexc) return fail(RH_EINVAL, "%s: the output tables may not alias", who);
+  return RH_OK;
+}
+}  // namespace
+
+int rh_bem_excitation(rh_ctx* ctx, int nw, const double* k, int nhb, const double* bem_headings_deg,
+                      const rh_c128* X_BEM, int nh, const double* beta, double heading_adjust_deg, double x_ref,
+                      double y_ref, const rh_c128* finer_in, rh_c128* fbem_out, rh_c128* fexc_out, rh_stream stream) {
+  if (!ctx) return fail(RH_EINVAL, "rh_bem_excitation: null context");
+  rh_bem_design d;
+  d.nw = nw, d.nhb = nhb, d.nh = nh, d.pad_ = 0;
+  d.heading_adjust_deg = heading_adjust_deg, d.x_ref = x_ref, d.y_ref = y_ref;
+  d.k = k, d.headings_deg = bem_headings_deg, d.X = X_BEM, d.beta = beta;
+  d.finer = finer_in, d.fbem = fbem_out, d.fexc = fexc_out;
+  if (int r = check_bem_design(d, "rh_bem_excitation")) return r;
+  RH_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(rh::k_bem_excitation, dim3((nw + 255) / 256, nh), dim3(256), 0, (hipStream_t)stream, d);
+  RH_HIP(hipGetLastError());
+  return RH_OK;
+}
+
+int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* designs, const rh_bem_design* designs_dev,
+                            rh_stream stream) {
+  if (!ctx || !designs || !designs_dev) return fail(RH_EINVAL, "rh_bem_excitation_batch: null argument");
+  if (ndesign < 1) return ndesign == 0 ? RH_OK : fail(RH_EINVAL, "rh_bem_excitation_batch: ndesign=%d", ndesign);
+  int nwmax = 0, nhmax = 0;
+  for (int i = 0; i < ndesign; ++i) {
+    const rh_bem_design& d = designs[i];
+    if (d.nhb == 0) continue;   // a design without BEM excitation
+    if (int r = check_bem_design(d, "rh_bem_excitation_batch")) return r;
+    nwmax = d.nw > nwmax ? d.nw : nwmax;
+    nhmax = d.nh > nhmax ? d.nh : nhmax;
+  }
+  if (nwmax == 0) return RH_OK;
+  RH_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(rh::k_bem_excitation_batch, dim3((nwmax + 255) / 256, nhmax, ndesign), dim3(256), 0,
+                     (hipStream_t)stream, designs_dev);
+  RH_HIP(hipGetLastError());
+  return RH_OK;
 }
 
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,

@@ -59,6 +59,12 @@ class RhQtfDesign(ctypes.Structure):
                 ("kray", _p), ("hank", _p), ("order", ctypes.c_int)]
 
 
+class RhBemDesign(ctypes.Structure):
+    _fields_ = [("nw", ctypes.c_int), ("nhb", ctypes.c_int), ("nh", ctypes.c_int), ("pad_", ctypes.c_int),
+                ("heading_adjust_deg", ctypes.c_double), ("x_ref", ctypes.c_double), ("y_ref", ctypes.c_double),
+                ("k", _p), ("headings_deg", _p), ("X", _p), ("beta", _p), ("finer", _p), ("fbem", _p), ("fexc", _p)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -87,6 +93,9 @@ def lib():
                 "rh_ctx_destroy": [_p],
                 "rh_wave_tables": [_p, ctypes.POINTER(RhDesign), _p, _p, _p, _p, _p],
                 "rh_wave_tables_batch": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, _p, ctypes.c_int, _p],
+                "rh_bem_excitation": [_p, ctypes.c_int, _p, ctypes.c_int, _p, _p, ctypes.c_int, _p, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, _p, _p, _p, _p],
+                "rh_bem_excitation_batch": [_p, ctypes.c_int, ctypes.POINTER(RhBemDesign), _p, _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,

@@ -22,6 +22,19 @@ from .second_order import solve_batch_2nd
 from .solver import CaseSet
 
 
+def refuse_bem_files(designs, who):
+    """The native and light preparations build M, B and the excitation from the members alone
+    (rh_prep knows nothing of coefficient files): a design that brings them (potFirstOrder = 1,
+    or potModMaster 2 / 3, which take the members' strip-theory inertia away) is refused by name."""
+    for d in {id(d): d for d in designs}.values():     # (a sweep passes one base dict many times)
+        plat = (d or {}).get("platform") or {}
+        first, master = plat.get("potFirstOrder"), plat.get("potModMaster")     # (absent in a sweep's designs: cheap)
+        if (first and int(first) > 0) or (master and int(master) in (2, 3)):
+            raise NotImplementedError(f"{who}: potential-flow coefficient files (potFirstOrder: 1, potModMaster 2 / 3) "
+                                      "need the full design models (DesignBatch(designs, native=False, light=False)): "
+                                      "A_BEM, B_BEM and X_BEM are read there")
+
+
 class DesignBatch:
     """Prepared single-FOWT designs sharing one frequency grid.
 
@@ -54,6 +67,7 @@ class DesignBatch:
             raise ValueError("statics: one dict for all designs or one per design")
         self._prepared = None
         if native or specs is not None or light or prepared is not None:
+            refuse_bem_files(designs, "DesignBatch")
             for d in {id(d): d for d in designs}.values():     # (a sweep passes one base dict many times)
                 if get_from_dict((d or {}).get("platform") or {}, "potSecOrder", dtype=int, default=0) > 0:
                     raise NotImplementedError("DesignBatch: second-order loads (potSecOrder > 0) need the full design "
@@ -262,6 +276,7 @@ def solve_sweep(designs, statics, design_idx, state_idx, sea_states, device=0, p
     per block, the host seconds of (design preparation, case set + tables + uploads, solve
     enqueue, DesignBatch host part, DesignBatch upload part)."""
     import gc
+    refuse_bem_files(designs, "solve_sweep")
     was = gc.isenabled()
     gc.disable()     # a full collection inside the pipeline stalled the host for 50-65 ms (profiles/r06_v1)
     try:
@@ -388,6 +403,7 @@ def prepare_native(designs, statics=None, r6=None, pool=None, specs=None, thread
     from .hydro_math import wave_numbers
     from .native_prep import PreparedDesigns
     t0 = time.perf_counter()
+    refuse_bem_files(designs, "prepare_native")
     if isinstance(statics, dict) or statics is None:
         statics = [statics] * len(designs)
     w = Model.frequency_grid(designs[0])
@@ -427,6 +443,7 @@ def prepare_design(job):
     f = m.fowtList[0]
     f.setPosition(np.zeros(6) if r6 is None else np.asarray(r6, dtype=float))
     f.calcStatics()
+    f.calcBEM()                # as analyzeCases (raft/raft_model.py:258-263): potModMaster 3 sorts the files' headings
     f.calcHydroConstants()
     f.host_tables()            # the device-table layout, built here too (travels with the FOWT)
     return HostDesign(m) if light else m

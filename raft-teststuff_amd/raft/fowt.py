@@ -8,10 +8,13 @@ the per-design preparation (members, node tables, linear matrices) and the devic
 The statics (member inertia / hydrostatics / RNA) are computed on
 the host by raft/statics.py, the mooring by raft/mooring.py, and an operating rotor's
 aero-servo coefficients by raft/rotor.py (its blade-element solve is CCBlade's, a dependency of
-the reference that has to be installed for wind > 0).  Not built here: BEM
-(pyHAMS), BEM coefficient files (potFirstOrder=1) and underwater rotors.  External .12d QTFs
-(potSecOrder=2) are read on the host (qtf_io.read_qtf12d) and applied on the device
-(rh_force_2nd).
+the reference that has to be installed for wind > 0).  First-order potential-flow coefficient
+files (potFirstOrder=1, WAMIT .1/.3) are read on the host (bem_io.py): their added mass and
+radiation damping enter the per-bin M and B, their excitation is interpolated in heading, rotated
+and phased on the device (rh_bem_excitation).  External .12d QTFs (potSecOrder=2) are read on the
+host (qtf_io.read_qtf12d) and applied on the device (rh_force_2nd).  Not built here (SURVEY.md
+§2): running a BEM solver (pyHAMS meshing and run_hams; such configurations raise) and underwater
+rotors.
 """
 import os
 import ctypes
@@ -79,6 +82,7 @@ class FOWT:
         self.potModMaster = get_from_dict(plat, "potModMaster", dtype=int, default=0)
         dlsMax = get_from_dict(plat, "dlsMax", default=5.0)
         self.memberList = []
+        self.potMod = False                # any platform member modelled with potential flow (:209)
         self.nplatmems = 0                 # raft/raft_fowt.py:61-67
         self.ntowers = 0
         self.rnaList = []                  # RNA inertia/pose per rotor (raft/statics.py)
@@ -91,6 +95,7 @@ class FOWT:
                 mi["potMod"] = True
             if "dlsMax" not in mi:
                 mi["dlsMax"] = dlsMax
+            self.potMod = self.potMod or mi.get("potMod", False) == True   # noqa: E712 (the reference's test)
             headings = get_from_dict(mi, "heading", shape=-1, default=0.)
             for hd in np.atleast_1d(headings):
                 self.memberList.append(Member(mi, self.nw, heading=float(hd) + heading_adjust))
@@ -156,6 +161,14 @@ class FOWT:
         self.f_aero0 = np.zeros([6, self.nrotors])
         self.A_BEM = np.zeros([6, 6, self.nw])
         self.B_BEM = np.zeros([6, 6, self.nw])
+        self.X_BEM = None                  # [nhb, 6, nw] excitation coefficients, each in its heading's wave frame
+        self.BEM_headings = None           # [nhb] their headings [deg, 0..360)
+        self.potFirstOrder = get_from_dict(plat, "potFirstOrder", dtype=int, default=0)   # raft/raft_fowt.py:222-227
+        if self.potFirstOrder == 1:
+            if "hydroPath" not in plat:
+                raise Exception("If potFirstOrder==1, then hydroPath must be specified in the platform input.")
+            self.hydroPath = plat["hydroPath"]
+            self.readHydro()
         self.A_hydro_morison = np.zeros([6, 6])
         self.B_gyro = np.zeros([6, 6, max(self.nrotors, 1)])
         self.A_aero = np.zeros([6, 6, self.nw, self.nrotors])
@@ -312,6 +325,43 @@ class FOWT:
         if had_aero or np.any(self.A_aero) or np.any(self.B_aero) or np.any(self.B_gyro):
             self._dd = self._host = None          # the per-bin M and B of the device design change
 
+    def bem_excitation(self):
+        """Whether calcHydroExcitation adds the potential-flow excitation F_BEM
+        (raft/raft_fowt.py:1039): only with potMod members or potModMaster 2 / 3.  So
+        potFirstOrder 1 with potModMaster 1 gets A_BEM and B_BEM on top of the strip-theory added
+        mass and no F_BEM, as in the reference."""
+        return bool(self.potMod or self.potModMaster in [2, 3])
+
+    def _bem_solver_needed(self):
+        return bool(self.potMod and self.potModMaster in [0, 2])
+
+    def readHydro(self):
+        """raft/raft_fowt.py:719-767: A_BEM, B_BEM, X_BEM and BEM_headings (unsorted) from the
+        WAMIT-format files hydroPath.1 / .3 (bem_io.py), on this FOWT's frequency grid."""
+        from .bem_io import bem_tables
+        self.A_BEM, self.B_BEM, self.X_BEM, self.BEM_headings = bem_tables(self.hydroPath, self.w, self.rho_water,
+                                                                           self.g, sort_headings=False)
+        self._dd = self._host = None
+
+    def calcBEM(self, dw=0, wMax=0, wInf=10.0, dz=0, da=0, headings=[0], meshDir=None):
+        """raft/raft_fowt.py:568-714 without the BEM solver run: with potModMaster 3 the
+        coefficient files of hydroPath are read again, the headings sorted; configurations the
+        reference meshes and runs HAMS for (potMod members with potModMaster 0 or 2) raise."""
+        if self._bem_solver_needed():
+            raise NotImplementedError(
+                "calcBEM: potMod members with potModMaster 0 or 2 need a BEM solver run (pyHAMS meshing and "
+                "run_hams), which is outside the accelerated path; supply WAMIT .1/.3 files through hydroPath with "
+                "potFirstOrder: 1 and potModMaster: 3, or use strip theory (potModMaster: 1)")
+        if self.potModMaster != 3:
+            return
+        if self.potFirstOrder != 1:
+            raise ValueError("potModMaster: 3 reads the platform's first-order coefficients from hydroPath, which is "
+                             "only taken with potFirstOrder: 1; set potFirstOrder: 1 and hydroPath")
+        from .bem_io import bem_tables
+        self.A_BEM, self.B_BEM, self.X_BEM, self.BEM_headings = bem_tables(self.hydroPath, self.w, self.rho_water,
+                                                                           self.g, sort_headings=True)
+        self._dd = self._host = None
+
     def calcHydroConstants(self):
         """raft/raft_fowt.py:848-880 (strip-theory members)."""
         self.A_hydro_morison = np.zeros([6, 6])
@@ -358,8 +408,9 @@ class FOWT:
 
     def calcHydroExcitation(self, case, memberList=[], dgamma=0):
         """Sea state + strip-theory inertial excitation (raft/raft_fowt.py:972-1149) on the
-        device.  Sets beta, S, zeta, F_hydro_iner [nWaves,6,nw], F_BEM and the per-member
-        kinematics mem.u/ud/pDyn like the reference."""
+        device.  Sets beta, S, zeta, F_hydro_iner [nWaves,6,nw], F_BEM [nWaves,6,nw] (the
+        potential-flow excitation of a design with coefficient files, else zero) and the
+        per-member kinematics mem.u/ud/pDyn like the reference."""
         import torch
         dd = self.device_design()
         hd, spec, Hs, Tp, gam = self._sea_state(case)
@@ -382,7 +433,10 @@ class FOWT:
         self.S = S.cpu().numpy()
         self.zeta = zeta.cpu().numpy().astype(complex)
         self.F_hydro_iner = F.cpu().numpy()
-        self.F_BEM = np.zeros([nW, 6, self.nw], dtype=complex)
+        if dd.bem is not None:     # potential-flow excitation (raft/raft_fowt.py:1039-1093; rh_bem_excitation)
+            self.F_BEM = (dd.fbem.index_select(0, hidx) * zeta[:, None, :]).cpu().numpy()
+        else:
+            self.F_BEM = np.zeros([nW, 6, self.nw], dtype=complex)
         self._fill_member_kinematics(memberList, dd, heads, zeta)
 
     def _fill_member_kinematics(self, memberList, dd, heads, zeta):

@@ -174,7 +174,7 @@ class Model:
                     fm, f = fowt.calcHydroForce_2ndOrd(fowt.beta[ih], fowt._S_dev[ih])
                     fowt.Fhydro_2nd_mean[ih], fowt.Fhydro_2nd[ih] = fm, f
                     fowt._f2nd_w[ih] = fowt._f2nd_dev.to(torch.complex128)
-                F = dd.finer[fowt._heads[ih]] * fowt._zeta_dev[ih][None, :] + Fd
+                F = dd.excitation_table()[fowt._heads[ih]] * fowt._zeta_dev[ih][None, :] + Fd
                 if fowt._f2nd_w[ih] is not None:
                     F = F + fowt._f2nd_w[ih]
                 Fw.append(F)
@@ -456,6 +456,7 @@ class Model:
         for fowt in self.fowtList:
             fowt.setPosition([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0])
             fowt.calcStatics()
+            fowt.calcBEM(meshDir=meshDir)          # :258-263 (coefficient files only: no BEM solver run)
         for iCase in range(nCases):
             if display > 0:
                 print(f"\n--------------------- Running Case {iCase + 1} ----------------------")
@@ -506,6 +507,7 @@ class Model:
         if self.nFOWT != 1:
             return self.analyzeArrayBatch(cases, tol=tol, host=host)
         fowt = self.fowtList[0]
+        self._calc_bem_once()
         seas = [self._case_sea_states(c) for c in cases]
         nws = np.array([len(s[0]) for s in seas], dtype=np.int64)
         if fowt.potSecOrder == 1 and len(cases) and nws.max() > 1:
@@ -543,6 +545,15 @@ class Model:
         if multi:
             self._extra_sea_states(res, views, idx, seas, nws, want)
         return res.host() if host else res
+
+    def _calc_bem_once(self):
+        """FOWT.calcBEM as analyzeCases calls it (raft/raft_model.py:258-263), for the batched entry
+        points: potModMaster 3 reads the coefficient files with sorted headings (once per FOWT and
+        pose of the tables: the files do not change), configurations that need a BEM solver run raise."""
+        for fowt in self.fowtList:
+            if fowt._bem_solver_needed() or (fowt.potModMaster == 3 and not getattr(fowt, "_bem_sorted", False)):
+                fowt.calcBEM()
+                fowt._bem_sorted = True
 
     @staticmethod
     def _case_sea_states(case):
@@ -636,6 +647,7 @@ class Model:
         every sea state is tabulated here, before any descriptor is made."""
         import torch
         nf, n = self.nFOWT, len(cases)
+        self._calc_bem_once()
         dds = [f.device_design() for f in self.fowtList]   # (node counts may differ: Bmat rows padded to the largest)
         seas = [self._case_sea_states(c) for c in cases]
         nws = np.array([len(x[0]) for x in seas], dtype=np.int64)

@@ -14,6 +14,11 @@ One process per GPU, torch.distributed with backend "nccl" (RCCL over xGMI).  Tw
   exchanged with one all_gather of each rank's packed upper-triangle pairs (exact copies),
   then the Hermitian lower triangle is filled on every rank.
 
+A design with potential-flow coefficient files (potFirstOrder = 1) needs nothing extra here: the
+case- and bin-sharded solves take the design through its descriptor, which carries the per-bin M
+and B (A_BEM, B_BEM) and points `finer` at the table that includes the BEM excitation
+(prep.DeviceDesign; tests/test_gpu_bem.py), and the QTF rows are computed from a given RAO.
+
 The collective helpers take any process group; tests run them with gloo on the CPU.
 """
 import numpy as np

@@ -5,6 +5,10 @@ Layout in HBM (one design, nn submerged nodes, nw bins, nh headings):
   imat_mcf  complex128 [nn][9][nw]        only when some member uses MacCamy-Fuchs
   uhat      complex128 [nh][nn][3][nw]    unit-amplitude wave velocity, bins contiguous
   finer     complex128 [nh][6][nw]        unit-amplitude inertial excitation
+  fbem, fexc complex128 [nh][6][nw]       only for a design with BEM excitation (potFirstOrder = 1 files and
+                                          potMod members / potModMaster 2, 3): the potential-flow excitation
+                                          per unit amplitude and finer + fbem (rh_bem_excitation); such a
+                                          design's descriptor points `finer` at fexc
   M, B      float64 [36] or [nw][36]      M_lin, B_lin (raft/raft_model.py:911-912)
   C         float64 [36]                  C_lin (raft/raft_model.py:913)
 uhat is what the case kernel streams twice per drag iteration; bins are contiguous so a
@@ -126,7 +130,28 @@ def host_tables(fowt):
         layout[name] = (off, a.shape)
         off += a.size
     packed = np.concatenate([np.ascontiguousarray(a).ravel() for _, a in parts])
-    return dict(packed=packed, layout=layout, imat=imat, mstart=mstart, nn=nn, nm=nm, per_bin=per_bin)
+    out = dict(packed=packed, layout=layout, imat=imat, mstart=mstart, nn=nn, nm=nm, per_bin=per_bin)
+    bem = bem_host_tables(fowt)
+    if bem is not None:
+        out["bem"] = bem
+    return out
+
+
+def bem_host_tables(fowt):
+    """What rh_bem_excitation reads of a design whose excitation includes the potential-flow
+    part (FOWT.bem_excitation, raft/raft_fowt.py:1039): X_BEM [nhb,6,nw], its headings [deg] and
+    the FOWT's heading_adjust [deg] and array position.  None for every other design."""
+    uses = getattr(fowt, "bem_excitation", None)
+    if uses is None or not uses():
+        return None
+    X = getattr(fowt, "X_BEM", None)
+    if X is None:
+        raise NotImplementedError(
+            "this design's first-order wave excitation comes from a BEM solver run (potMod members, or potModMaster "
+            "2 / 3, without coefficient files): pyHAMS meshing and run_hams are outside the accelerated path; supply "
+            "WAMIT .1/.3 files through hydroPath with potFirstOrder: 1")
+    return dict(X=np.ascontiguousarray(X, dtype=complex), headings=np.ascontiguousarray(fowt.BEM_headings, dtype=float),
+                heading_adjust=float(fowt.heading_adjust), x_ref=float(fowt.x_ref), y_ref=float(fowt.y_ref))
 
 
 class DeviceDesign:
@@ -157,13 +182,24 @@ class DeviceDesign:
         self.uhat = None
         self.finer = None
         self.kproj = None
+        # BEM excitation (host_tables' "bem"): X_BEM and its headings on the device; fbem / fexc follow
+        # the wave tables.  None for every other design, which then takes none of the BEM steps.
+        self.bem = None
+        b = h.get("bem")
+        if b is not None:
+            self.bem = dict(X=torch.tensor(b["X"], dtype=torch.complex128, device=self.device).contiguous(),
+                            headings=torch.tensor(b["headings"], dtype=torch.float64, device=self.device),
+                            nhb=len(b["headings"]), heading_adjust=b["heading_adjust"], x_ref=b["x_ref"],
+                            y_ref=b["y_ref"])
+        self.fbem = None
+        self.fexc = None
 
-    _TABLES = ("uhat", "kproj", "finer")
+    _TABLES = ("uhat", "kproj", "finer", "fbem", "fexc")
 
     def __getattr__(self, name):
         tab = self.__dict__.get("_tab")
         if tab is not None and name in self._TABLES:     # a view of the batch's shared tables, made on first use
-            v = self._tab_view(name)
+            v = self._tab_view(name) if name in tab else None
             self.__dict__[name] = v
             return v
         lay = self.__dict__.get("_layout")
@@ -180,8 +216,9 @@ class DeviceDesign:
 
     def set_tables(self, tab, headings):
         """Point the wave tables at slices of shared allocations without making the views:
-        tab[name] = (flat complex128 tensor, element offset, shape) for uhat, kproj, finer
-        (raft/prep.py tabulate_batch; the views appear on first access)."""
+        tab[name] = (flat complex128 tensor, element offset, shape) for uhat, kproj, finer (and
+        fbem, fexc of a design with BEM excitation) (raft/prep.py tabulate_batch; the views appear
+        on first access)."""
         for name in self._TABLES:
             self.__dict__.pop(name, None)
         self._tab = tab
@@ -190,9 +227,38 @@ class DeviceDesign:
 
     def _tab_ptr(self, name):
         if name not in self.__dict__ and self.__dict__.get("_tab") is not None:
+            if name not in self._tab:
+                return None
             base, off, _ = self._tab[name]
             return ctypes.c_void_p(base.data_ptr() + 16 * off)
         return N.ptr(self.__dict__.get(name))
+
+    def _exc_name(self):
+        """The table the descriptor's `finer` points at: fexc for a design with BEM excitation."""
+        return "fexc" if self.bem is not None else "finer"
+
+    def excitation_table(self):
+        """Unit-amplitude first-order wave excitation [nh, 6, nw] the solver paths use: the
+        strip-theory table, plus the potential-flow part for a design with BEM excitation."""
+        return self.fexc if self.bem is not None else self.finer
+
+    def bem_record(self):
+        """This design's rh_bem_design values (a dict; nhb = 0 without BEM excitation)."""
+        if self.bem is None:
+            return dict(nhb=0)
+        b = self.bem
+        return dict(nw=self.nw, nhb=b["nhb"], nh=len(self.headings), heading_adjust_deg=b["heading_adjust"],
+                    x_ref=b["x_ref"], y_ref=b["y_ref"], k=self._addr("k").value, headings_deg=b["headings"].data_ptr(),
+                    X=b["X"].data_ptr(), beta=self._beta_keep.data_ptr(), finer=self._tab_ptr("finer").value,
+                    fbem=self._tab_ptr("fbem").value, fexc=self._tab_ptr("fexc").value)
+
+    def _bem_tables(self, stream):
+        """fbem and fexc of the tabulated headings from the strip-theory finer (rh_bem_excitation,
+        after rh_wave_tables on the same stream)."""
+        r = self.bem_record()
+        N.check(N.lib().rh_bem_excitation(N.context(self.dev_index), r["nw"], r["k"], r["nhb"], r["headings_deg"],
+                                          r["X"], r["nh"], r["beta"], r["heading_adjust_deg"], r["x_ref"], r["y_ref"],
+                                          r["finer"], r["fbem"], r["fexc"], stream), "rh_bem_excitation")
 
     def _addr(self, name):
         return ctypes.c_void_p(self._packed.data_ptr() + 8 * self._layout[name][0])
@@ -217,7 +283,7 @@ class DeviceDesign:
         d.w, d.k, d.node = self._addr("w"), self._addr("k"), self._addr("node")
         d.nm, d.memb, d.mstart = self.nm, self._addr("memb"), N.ptr(self.mstart)
         d.imat_mcf = N.ptr(self.imat)
-        d.uhat, d.finer, d.kproj = self._tab_ptr("uhat"), self._tab_ptr("finer"), self._tab_ptr("kproj")
+        d.uhat, d.finer, d.kproj = self._tab_ptr("uhat"), self._tab_ptr(self._exc_name()), self._tab_ptr("kproj")
         d.M, d.B, d.C = self._addr("M"), self._addr("B"), self._addr("C")
         return d
 
@@ -235,6 +301,9 @@ class DeviceDesign:
             self.uhat = torch.empty([nh, max(self.nn, 1), 3, self.nw], dtype=torch.complex128, device=self.device)
             self.finer = torch.empty([nh, 6, self.nw], dtype=torch.complex128, device=self.device)
             self.kproj = torch.empty([nh, max(self.nn, 1), 3, self.nw], dtype=torch.complex128, device=self.device)
+            if self.bem is not None:
+                self.fbem = torch.empty([nh, 6, self.nw], dtype=torch.complex128, device=self.device)
+                self.fexc = torch.empty([nh, 6, self.nw], dtype=torch.complex128, device=self.device)
             self.headings = tuple(allh)
             self._tabver = getattr(self, "_tabver", 0) + 1
             beta_t = torch.tensor(allh, dtype=torch.float64, device=self.device)
@@ -244,6 +313,8 @@ class DeviceDesign:
                                            N.stream_handle(torch, self.device)),
                     "rh_wave_tables")
             self._beta_keep = beta_t
+            if self.bem is not None:
+                self._bem_tables(N.stream_handle(torch, self.device))
         return [self.headings.index(b) for b in betas]
 
     def retabulate(self, stream=None):
@@ -256,12 +327,16 @@ class DeviceDesign:
         s = stream if stream is not None else N.stream_handle(self.torch, self.device)
         N.check(N.lib().rh_wave_tables(N.context(self.dev_index), ctypes.byref(d), N.ptr(self._beta_keep),
                                        N.ptr(self.uhat), N.ptr(self.finer), N.ptr(self.kproj), s), "rh_wave_tables")
+        if self.bem is not None:
+            self._bem_tables(s)
 
 
-def descriptor_block(designs):
+def descriptor_block(designs, strip_finer=False):
     """The rh_design descriptors of many designs as one ctypes array, filled column-wise in a
     numpy record array of rh_design's layout (DeviceDesign._make_struct's values, without a
-    ctypes field write per field and design); each design's descriptor cache is set from it."""
+    ctypes field write per field and design); each design's descriptor cache is set from it.
+    strip_finer: `finer` is the strip-theory table of every design, also of one with BEM
+    excitation (the descriptors rh_wave_tables_batch writes through; not cached)."""
     rec = np.zeros(len(designs), dtype=np.dtype(N.RhDesign))
     cols = {k: [] for k in rec.dtype.names}
     for d in designs:
@@ -270,7 +345,8 @@ def descriptor_block(designs):
         for k in ("w", "k", "node", "memb", "M", "B", "C"):
             cols[k].append(base + 8 * lay[k][0])
         for k in ("uhat", "finer", "kproj"):
-            cols[k].append(d._tab_ptr(k).value or 0)
+            t = d._tab_ptr(d._exc_name() if k == "finer" and not strip_finer else k)
+            cols[k].append((t.value if t is not None else 0) or 0)
         cols["mstart"].append(d.mstart.data_ptr())
         cols["imat_mcf"].append(d.imat.data_ptr() if d.imat is not None else 0)
         cols["nw"].append(d.nw)
@@ -287,6 +363,8 @@ def descriptor_block(designs):
         rec[k] = v
     arr = (N.RhDesign * len(designs)).from_buffer(rec)
     arr._rec = rec                                         # (the array's memory)
+    if strip_finer:
+        return arr
     for j, d in enumerate(designs):
         d._struct = ((d.__dict__.get("_tabver", 0), d.__dict__.get("kproj"), d.headings), N.RhDesign.from_buffer_copy(arr[j]))
     return arr
@@ -297,7 +375,10 @@ def tabulate_batch(designs, design_idx, betas, launch_stream=None):
     launch, for designs that have none yet (a fresh design sweep).  Returns the heading
     index of every case in its design's tables.  Tables of all designs share three device
     allocations; each DeviceDesign holds views.  launch_stream: run the launch there (after
-    this stream's uploads, through an event) instead of on the current stream."""
+    this stream's uploads, through an event) instead of on the current stream.
+    Designs with BEM excitation get fbem and fexc from one rh_bem_excitation_batch launch behind
+    the tables' (their strip-theory finer is written first, through descriptors that point at
+    it); a batch without such a design takes none of these steps."""
     from .sweep_block import table_plan
     torch = designs[0].torch
     dev = designs[0].device
@@ -309,18 +390,24 @@ def tabulate_batch(designs, design_idx, betas, launch_stream=None):
     U = torch.empty([sum(rows)], **c128)
     K = torch.empty([sum(rows)], **c128)
     Fi = torch.empty([int(nh.sum()) * 6 * nw], **c128)
+    any_bem = any(d.bem is not None for d in sel)
+    if any_bem:
+        Fb = torch.empty([int(nh.sum()) * 6 * nw], **c128)
+        Fx = torch.empty([int(nh.sum()) * 6 * nw], **c128)
     ou = of = 0
     for j, (d, k) in enumerate(zip(sel, nh)):
         k = int(k)
         hs = bm[j, :k]
         shp = (k, max(d.nn, 1), 3, nw)
-        d.set_tables({"uhat": (U, ou, shp), "kproj": (K, ou, shp), "finer": (Fi, of, (k, 6, nw))},
-                     [float(b) for b in hs])
+        tab = {"uhat": (U, ou, shp), "kproj": (K, ou, shp), "finer": (Fi, of, (k, 6, nw))}
+        if d.bem is not None:
+            tab.update(fbem=(Fb, of, (k, 6, nw)), fexc=(Fx, of, (k, 6, nw)))
+        d.set_tables(tab, [float(b) for b in hs])
         ou, of = ou + rows[j], of + k * 6 * nw
     beta_t = torch.tensor(bm, dtype=torch.float64, device=dev)
     for j, d in enumerate(sel):
         d._beta_keep = beta_t[j, :int(nh[j])]
-    arr = descriptor_block(sel)
+    arr = descriptor_block(sel, strip_finer=True) if any_bem else descriptor_block(sel)
     if launch_stream is not None:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
@@ -330,4 +417,20 @@ def tabulate_batch(designs, design_idx, betas, launch_stream=None):
         s = N.stream_handle(torch, dev)
     N.check(N.lib().rh_wave_tables_batch(N.context(sel[0].dev_index), arr, len(sel), N.ptr(beta_t), hstride, s),
             "rh_wave_tables_batch")
+    if any_bem:
+        rec = np.zeros(len(sel), dtype=np.dtype(N.RhBemDesign))
+        for j, d in enumerate(sel):
+            for key, v in d.bem_record().items():
+                rec[key][j] = v
+        rec_dev = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        if launch_stream is not None:          # the records' upload ran on the current stream
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            launch_stream.wait_event(ev)
+        N.check(N.lib().rh_bem_excitation_batch(N.context(sel[0].dev_index), len(sel),
+                                                (N.RhBemDesign * len(sel)).from_buffer(rec), N.ptr(rec_dev), s),
+                "rh_bem_excitation_batch")
+        for d in sel:
+            d._bem_rec_keep = rec_dev          # read by the launch: kept with the designs' tables
+        descriptor_block(sel)                  # the designs' own descriptors: `finer` at fexc
     return head
