@@ -170,8 +170,11 @@ int rh_version(void);
 
 /* Kernel selection for rh_solve_cases on this context (not part of the reference API):
  * 0 = automatic (the LDS-resident fast path when nw <= 1024 and the node tables fit in LDS;
- * else the general kernel), 1 = always the general kernel.  Used by the parity tests to
- * cross-check the device paths on the same inputs.  (Builds with -DRH_VARIANTS, made by
+ * else the general kernel), 1 = always the general kernel, 6 = automatic, with the fast path
+ * treating every node as one that needs its axial wave-table row (what a design with
+ * Cd_q != 0 on every member runs; by default it streams that row only for nodes with axial side
+ * drag or end drag, the others' axial terms being exact zeros: same bits either way).  Used by
+ * the parity tests to cross-check the device paths on the same inputs.  (Builds with -DRH_VARIANTS, made by
  * tools/build_variants.sh for on-box A/B timing only, also accept 2..5: the lock-step grouped
  * kernel, the lane-pair kernel and the two-pass launch, all measured slower) */
 int rh_set_solver(rh_ctx* ctx, int which);

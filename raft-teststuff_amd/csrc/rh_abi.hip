@@ -59,6 +59,7 @@ struct rh_ctx {
   int cur = 0;                          // slot of the last staging
   // tuning / cross-check knobs (per context: the ABI has no mutable process globals)
   bool force_general = false;   // rh_set_solver(ctx, 1): always use k_solve_cases (parity cross-checks)
+  bool all_axial = false;       // rh_set_solver(ctx, 6): k_solve_lds streams every node's axial row (cross-checks)
 #ifdef RH_VARIANTS
   bool a0 = false;              // rh_set_a0: iteration-0 phase A of the fast path as a batch GEMM (rh_a0.hip;
                                 // measured slower than the per-case phase A)
@@ -220,19 +221,20 @@ int rh_version(void) { return 7; }
 int rh_set_solver(rh_ctx* ctx, int which) {
   if (!ctx) return fail(RH_EINVAL, "rh_set_solver: null context");
 #ifdef RH_VARIANTS
-  if (which < 0 || which > 5)
+  if (which < 0 || which > 6)
     return fail(RH_EINVAL,
                 "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 2 = ungrouped, 3 = k_solve_pair, "
-                "4 / 5 = ungrouped, k_solve_lds in one / two passes)", which);
-  ctx->no_group = which >= 2;
+                "4 / 5 = ungrouped, k_solve_lds in one / two passes, 6 = auto with every axial row)", which);
+  ctx->no_group = which >= 2 && which != 6;
   ctx->use_pair = which == 3 || (which == 0 && RH_PAIR_ON);
   ctx->two_pass = which == 5 || (which != 4 && RH_TWO_PASS);
 #else
-  if (which < 0 || which > 1)
-    return fail(RH_EINVAL, "rh_set_solver: which=%d (0 = auto, 1 = general kernel; the grouped, lane-pair and "
-                "two-pass kernels are tools/ubench variant builds)", which);
+  if (which != 0 && which != 1 && which != 6)
+    return fail(RH_EINVAL, "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 6 = auto with every axial row; "
+                "the grouped, lane-pair and two-pass kernels are tools/ubench variant builds)", which);
 #endif
   ctx->force_general = which == 1;
+  ctx->all_axial = which == 6;
   return RH_OK;
 }
 
@@ -471,6 +473,7 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
   a.c = *cases;
   a.o = *out;
   a.bmat_nn = nnmax;
+  a.all_axial = ctx->all_axial ? 1 : 0;
   int nmmax = 0;
   for (int i = 0; i < ndesign; ++i) nmmax = designs[i].nm > nmmax ? designs[i].nm : nmmax;
 #ifdef RH_VARIANTS

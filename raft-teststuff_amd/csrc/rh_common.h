@@ -213,6 +213,9 @@ struct CaseArgs {
   // node stride of the Bmat output ([ncase][bmat_nn][9]): the largest nn of the call's designs,
   // so designs with different node counts share one output array (rh_solve_cases sets it)
   int bmat_nn = 0;
+  // 1 (rh_set_solver(ctx, 6)): k_solve_lds treats every node as one that needs its axial
+  // wave-table row, as a design with Cd_q != 0 on every member does (cross-checks of the skip)
+  int all_axial = 0;
 };
 constexpr int kCaseStopped = 9;   // internal status between the two passes (never returned)
 

@@ -12,6 +12,8 @@
 //     3-slot register ring: node n+2 is in flight while node n is reduced.
 //   * Per-node bin sums: a 6-step DPP wave reduction (VALU only, no LDS or SGPR traffic),
 //     one partial per wave, summed in wave order.  Fixed order, so results are deterministic.
+//   * The axial row of a node (projection 0) is read only where the node has axial side drag or
+//     end drag; elsewhere it would meet coefficients that are exact zeros (same bits without it).
 #include "rh_common.h"
 #ifdef RH_VARIANTS
 #include "../../tools/ubench/variants_src/rh_a0_common.h"   // k_a0_sums sums (rh_set_a0)
@@ -59,11 +61,15 @@ constexpr int kRingC = RH_RING_C; // ... of phase C (one bin per pass: less work
 #define RH_XI_STORE 1                 // 0: per-entry stores of passing entries; 1: while the iteration may be final; 2: traffic floor (A/B)
 #endif
 #define XI_STORE_MODE RH_XI_STORE
-#ifndef RH_A_BATCH
-#define RH_A_BATCH 0                  // > 0: phase-A nodes in batches of RH_A_BATCH, one tbfly16 per batch
-#endif
 #ifndef RH_A_PAIR
-#define RH_A_PAIR 1                   // 1: phase-A sums of two nodes per butterfly (tbfly6)
+#define RH_A_PAIR 1                   // 1: phase-A sums of two nodes per butterfly (tbfly4)
+#endif
+#ifndef RH_C_AXIAL
+#define RH_C_AXIAL 2                  // phase C's axial row of a node that does not need it: 0: loaded; 1: through a closed
+                                      // descriptor; 2: not loaded (uniform branch); 3: nor accumulated (A/B)
+#endif
+#ifndef RH_A_QUAD
+#define RH_A_QUAD 1                   // 1: phase-A transverse sums of four nodes per butterfly (tbfly8; ring depth 4)
 #endif
 #ifndef RH_LDS_LANE_BRANCH
 #define RH_LDS_LANE_BRANCH 0          // 1: the round-2 per-lane `continue` before the solve (A/B only)
@@ -169,31 +175,47 @@ __device__ __forceinline__ double tbfly3(double a, double b, double c, int lane)
 // value held by a lane after tbfly3: 2 f0 + f1 -> lane 0: a (0), lane 1: c (2), lane 2: b (1)
 __device__ __forceinline__ int tbfly3_index(int lane) { return 2 * (lane & 1) + ((lane >> 1) & 1); }
 
-// Six wave sums at once: the three sums of two nodes.  Transposing stages with tbfly16's lane
-// flags (partners i^1, i^2, i^7 within the 16-lane row): (a0, a1), (b0, b1), (c0, c1) -> three
-// values, (v0, v1), (v2, 0) -> two, then one; the row halves (i^15) hold the same value and
-// are added, then the rows (lane^16, lane^32).  9 exchanges instead of 2 x 7 for two tbfly3.
-struct Bfly6 {   // a lane's stage flags and the sum it holds after tbfly6 (formed once per phase A)
+// Four wave sums at once, no pad: the transverse sums (s_1, s_2) of two nodes, or the axial sums of
+// four.  Transposing stages with tbfly16's lane flags (partners i^1, i^2 within the 16-lane row):
+// (a, c), (b, d) -> two values, then one; the partners i^7 and i^15 hold the same value and are
+// added, then the rows (lane^16, lane^32).  7 exchanges.  Every value meets the partners ^1, ^2,
+// ^7, ^15, ^16, ^32 in that order whichever slot it is in (all commutative adds), so a wave sum's
+// bits do not depend on how the values are grouped.
+struct Bfly4 {   // a lane's stage flags and the value it holds after tbfly4 (formed once per phase A)
   bool f0, f1, f2;
-  int vi;         // 3 node + sum, or -1 (pad; lanes >= 8 hold copies)
+  int vi;        // 0 = a .. 3 = d, or -1 (lanes >= 4 hold copies)
+  int vi8;       // (tbfly8) 0 .. 7, or -1 (lanes >= 8 hold copies)
 };
-__device__ __forceinline__ Bfly6 bfly6_lane(int lane) {
+__device__ __forceinline__ Bfly4 bfly4_lane(int lane) {
   const int i = lane & 15;
-  Bfly6 b;
+  Bfly4 b;
   b.f0 = ((i ^ (i >> 2)) & 1) != 0;
   b.f1 = (((i >> 1) ^ (i >> 2)) & 1) != 0;
   b.f2 = (((i >> 2) ^ (i >> 3)) & 1) != 0;
-  b.vi = lane >= 8 ? -1 : b.f2 ? (b.f1 ? -1 : 3 * b.f0 + 2) : 3 * b.f0 + b.f1;
+  b.vi = lane >= 4 ? -1 : 2 * (lane & 1) + ((lane >> 1) & 1);
+  b.vi8 = lane >= 8 ? -1 : 4 * b.f0 + 2 * b.f1 + b.f2;
   return b;
 }
-__device__ __forceinline__ double tbfly6(double a0, double b0, double c0, double a1, double b1, double c1, const Bfly6& L) {
+// Eight wave sums at once (RH_A_QUAD: the transverse sums of four nodes): three transposing
+// stages (partners i^1, i^2, i^7), 8 -> 4 -> 2 -> 1 values, then i^15 and the rows as tbfly4:
+// the same partners in the same order for every value, 10 exchanges.
+__device__ __forceinline__ double tbfly8(const double (&u)[8], const Bfly4& L) {
   const bool f0 = L.f0, f1 = L.f1, f2 = L.f2;
-  const double v0 = (f0 ? a1 : a0) + dpp_mov<0xB1>(f0 ? a0 : a1);
-  const double v1 = (f0 ? b1 : b0) + dpp_mov<0xB1>(f0 ? b0 : b1);
-  const double v2 = (f0 ? c1 : c0) + dpp_mov<0xB1>(f0 ? c0 : c1);
-  const double w0 = (f1 ? v1 : v0) + dpp_mov<0x4E>(f1 ? v0 : v1);
-  const double w1 = (f1 ? 0.0 : v2) + dpp_mov<0x4E>(f1 ? v2 : 0.0);
-  double t = (f2 ? w1 : w0) + dpp_mov<0x141>(f2 ? w0 : w1);
+  double v[4], w[2];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) v[p] = (f0 ? u[p + 4] : u[p]) + dpp_mov<0xB1>(f0 ? u[p] : u[p + 4]);
+#pragma unroll
+  for (int p = 0; p < 2; ++p) w[p] = (f1 ? v[p + 2] : v[p]) + dpp_mov<0x4E>(f1 ? v[p] : v[p + 2]);
+  double t = (f2 ? w[1] : w[0]) + dpp_mov<0x141>(f2 ? w[0] : w[1]);
+  t += dpp_mov<0x140>(t);
+  return xsum32(xsum16(t));
+}
+__device__ __forceinline__ double tbfly4(double a, double b, double c, double d, const Bfly4& L) {
+  const bool f0 = L.f0, f1 = L.f1;
+  const double v0 = (f0 ? c : a) + dpp_mov<0xB1>(f0 ? a : c);
+  const double v1 = (f0 ? d : b) + dpp_mov<0xB1>(f0 ? b : d);
+  double t = (f1 ? v1 : v0) + dpp_mov<0x4E>(f1 ? v0 : v1);
+  t += dpp_mov<0x141>(t);
   t += dpp_mov<0x140>(t);
   return xsum32(xsum16(t));
 }
@@ -299,6 +321,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   const int head = a.c.head[ic];
   const size_t c6 = (size_t)ic * 6 * nw;
   const Buf bK = mkbuf(d.kproj + (size_t)head * nn * 3 * nw, (unsigned)nn * 3u * nw16);
+  // (RH_C_AXIAL == 1, A/B only) the same table with the bounds closed when `on` is false
+  // (uniform): every lane is then out of range and the load returns 0 without traffic, still one
+  // vector-memory operation; measured slower than a branch around the load
+  [[maybe_unused]] auto bK_if = [&](bool on) { return mkbuf(d.kproj + (size_t)head * nn * 3 * nw, on ? (unsigned)nn * 3u * nw16 : 0u); };
   const Buf bFe = mkbuf(d.finer + (size_t)head * 6 * nw, 6u * nw16);
   const bool has_fx = a.c.fext != nullptr;
   const Buf bFx = mkbuf(has_fx ? a.c.fext + c6 : nullptr, has_fx ? 6u * nw16 : 0u);
@@ -339,11 +365,26 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   double* lz = lw + NP * NWP;                      // [NP NWP] zeta per bin (pad bins: 0)
   double* mred = lz + NP * NWP;                    // [LW] per-wave max of tolCheck
   int* mstart = reinterpret_cast<int*>(mred + LW);  // [nm+1]
+  // Which nodes need their axial wave-table row (projection 0): those with axial side drag or
+  // end drag, AQ CDQ != 0 or AEND CDEND != 0 (node_bmat_f); for every other node the row enters
+  // the result only through coefficients that are exact zeros (Cd_q defaults to 0 and end areas
+  // are non-zero only at member ends and diameter steps: 4 of 53 nodes of C2).  Kept in the
+  // spare sixth double of the node's `al` row as two ints: [0] the flags of nodes n .. n + 31
+  // (bit 0: the node's own; one read serves a whole round of a prefetch ring), [1] entry k = n of
+  // the compact, node-ordered list of the axial nodes (-1 past its end).
+  int* ax = reinterpret_cast<int*>(al);
+  auto ax_win = [&](int n) { return n < nn ? __builtin_amdgcn_readfirstlane(ax[12 * n + 10]) : 0; };   // n uniform
+  auto ax_node = [&](int k) { return k < nn ? __builtin_amdgcn_readfirstlane(ax[12 * k + 11]) : -1; };   // k uniform
   int* sflag = mstart + nm + 1;                      // [2] vote words of even / odd iterations,
                                                      // [2]: it + 1 once a test of iteration it failed,
                                                      // [3 + (it & 1)]: waves done with phase C of iteration it
   load_mbc(d, mbc, tid);
-  for (int n = tid; n < nn; n += LT) nt[n] = node[RH_NF_T * nn + n];
+  for (int n = tid; n < nn; n += LT) {
+    nt[n] = node[RH_NF_T * nn + n];
+    const double aq = node[RH_NF_AQ * nn + n], cdq = node[RH_NF_CDQ * nn + n];
+    const double ae = node[RH_NF_AEND * nn + n], cde = node[RH_NF_CDEND * nn + n];
+    ax[12 * n + 10] = (a.all_axial || aq * cdq != 0.0 || ae * cde != 0.0) ? 1 : 0;
+  }
   for (int e = tid; e < 18 * nm; e += LT) mbf[e] = d.memb[(e % 18) * nm + e / 18];   // RH_MF_CQ0..C20: fields 0..17
   for (int e = tid; e <= nm; e += LT) mstart[e] = d.mstart[e];
   if (tid < 5) sflag[tid] = 0;
@@ -417,6 +458,26 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   double margin = resume && a.o.margin ? a.o.margin[ic] : INFINITY;
   const int itend = resume || stop_iter >= nloop ? nloop : stop_iter;
   __syncthreads();
+  for (int n = tid; n < nn; n += LT) {   // the list: node n goes to the entry of its rank
+    int rank = 0, nq = 0;
+    for (int k = 0; k < nn; ++k) {
+      const int f = ax[12 * k + 10] & 1;
+      nq += f;
+      rank += k < n ? f : 0;
+    }
+    if (ax[12 * n + 10] & 1) ax[12 * rank + 11] = n;
+    if (n >= nq) ax[12 * n + 11] = -1;
+  }
+  __syncthreads();
+  for (int n0 = 0; n0 < nn; n0 += LT) {   // the flag windows (a round reads only words not yet rewritten)
+    const int n = n0 + tid;
+    int w = 0;
+    for (int i = 0; i < 32; ++i)
+      if (n + i < nn) w |= (ax[12 * (n + i) + 10] & 1) << i;
+    __syncthreads();
+    if (n < nn) ax[12 * n + 10] = w;
+  }
+  __syncthreads();
   PROF_T(tp1);
   PROF_ADD(0, tp1 - tp0);
 
@@ -435,13 +496,23 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     for (int c = 0; c < 6; ++c) F[c] = mk(0, 0);
     {
       cd SQ = mk(0, 0), S1 = mk(0, 0), S2 = mk(0, 0), T1 = mk(0, 0), T2 = mk(0, 0);
-      auto load1 = [&](cd (&K)[3], int n) {
+      auto load1 = [&](cd (&K)[3], int n, bool axial) {
         const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
 #if RH_ABL_C_NOLOAD
         if (n >= kRingC) return;
 #endif
+        // the axial row only where it is needed (uniform branch; two-bin kernels): elsewhere
+        // K[0] = 0 meets A[0] = +0, and SQ (which starts at +0) keeps its bits
+#if RH_C_AXIAL == 1
+        K[0] = bld(NB > 1 ? bK_if(axial) : bK, vj, so);
+#elif RH_C_AXIAL >= 2
+        if (NB == 1 || axial) K[0] = bld(bK, vj, so);
+        else K[0] = mk(0.0, 0.0);
+#else
+        K[0] = bld(bK, vj, so);
+#endif
 #pragma unroll
-        for (int p = 0; p < 3; ++p) K[p] = bld(bK, vj, so + (unsigned)p * nw16);
+        for (int p = 1; p < 3; ++p) K[p] = bld(bK, vj, so + (unsigned)p * nw16);
       };
       int m = 0, mnext = nn > 0 ? mstart[1] : 0;
       auto fold = [&]() {   // close member m: F += sum of its nodes (as drag_exc_members)
@@ -458,7 +529,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         }
         SQ = S1 = S2 = T1 = T2 = mk(0, 0);
       };
-      auto step = [&](cd (&K)[3], int n) {
+      auto step = [&](cd (&K)[3], int n, [[maybe_unused]] bool axial, bool next_axial) {
         while (n == mnext) {   // uniform: member m ended before node n
           fold();
           ++m;
@@ -468,23 +539,31 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         const double A0 = A[0], A1 = A[1], A2 = A[2], A3 = A[3], A4 = A[4];
 #if RH_ABL_C_NOCOMP
         SQ = add(SQ, K[0]); S1 = add(S1, K[1]); S2 = add(S2, K[2]);
-        load1(K, n + kRingC);
+        load1(K, n + kRingC, next_axial);
         return;
+#endif
+#if RH_C_AXIAL == 3
+        if (NB == 1 || axial)   // uniform
 #endif
         SQ = add(SQ, scl(K[0], A0));
         S1 = add(S1, scl(K[1], A1));
         S2 = add(S2, scl(K[2], A2));
         T1 = add(T1, scl(K[1], A3));
         T2 = add(T2, scl(K[2], A4));
-        load1(K, n + kRingC);
+        load1(K, n + kRingC, next_axial);
       };
       cd K[kRingC][3];
+      static_assert(kRingC <= 32, "one flag window per ring round");
+      const int w0 = ax_win(0);
 #pragma unroll
-      for (int r = 0; r < kRingC; ++r) load1(K[r], r);
+      for (int r = 0; r < kRingC; ++r) load1(K[r], r, ((w0 >> r) & 1) != 0);
+      int wc = w0;   // the flags of the round's own nodes
       for (int n = 0; n < nn; n += kRingC) {
+        const int w = ax_win(n + kRingC);   // ... and of the nodes it requests
 #pragma unroll
         for (int r = 0; r < kRingC; ++r)
-          if (n + r < nn) step(K[r], n + r);
+          if (n + r < nn) step(K[r], n + r, ((wc >> r) & 1) != 0, ((w >> r) & 1) != 0);
+        wc = w;
       }
       if (nn > 0) fold();
     }
@@ -533,44 +612,60 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       }
       // (defined here, not just before their first use: left undefined, the register allocator
       // may keep the previous iteration's values live, and spill them, across phase C)
-      cd Bq[NB], B1[NB], B2[NB], E1[NB], E2[NB];
+      cd B1[NB], B2[NB], E1[NB], E2[NB];
 #pragma unroll
-      for (int j = 0; j < NB; ++j) Bq[j] = B1[j] = B2[j] = E1[j] = E2[j] = mk(0.0, 0.0);
-      auto member_terms = [&](int m) {
-        double cq[6], c1[6], c2[6];
+      for (int j = 0; j < NB; ++j) B1[j] = B2[j] = E1[j] = E2[j] = mk(0.0, 0.0);
+      auto bin_xi = [&](int j, cd (&X)[6]) {   // XiLast of bin j of this thread
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          if constexpr (GX) X[c] = XR[j][c];
+          else X[c] = xl[c * NWP + pb + LT * j];
+        }
+      };
+      auto member_terms = [&](int m) {   // the transverse terms of member m
+        double c1[6], c2[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-          cq[i] = mbf[18 * m + RH_MF_CQ0 + i];
           c1[i] = mbf[18 * m + RH_MF_C10 + i];
           c2[i] = mbf[18 * m + RH_MF_C20 + i];
         }
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-          const int b = pb + LT * j;
           cd X[6];
+          bin_xi(j, X);
+          cd A1 = mk(0, 0), A2 = mk(0, 0);
 #pragma unroll
           for (int c = 0; c < 6; ++c) {
-            if constexpr (GX) X[c] = XR[j][c];
-            else X[c] = xl[c * NWP + b];
-          }
-          cd Aq = mk(0, 0), A1 = mk(0, 0), A2 = mk(0, 0);
-#pragma unroll
-          for (int c = 0; c < 6; ++c) {
-            Aq = add(Aq, scl(X[c], cq[c]));
             A1 = add(A1, scl(X[c], c1[c]));
             A2 = add(A2, scl(X[c], c2[c]));
           }
           const cd D1 = add(add(scl(X[3], c2[0]), scl(X[4], c2[1])), scl(X[5], c2[2]));   // p2 . th
           const cd D2 = add(add(scl(X[3], c1[0]), scl(X[4], c1[1])), scl(X[5], c1[2]));   // p1 . th
-          const double w = lw[b];
-          Bq[j] = iw(w, Aq);
+          const double w = lw[pb + LT * j];
           B1[j] = iw(w, A1);
           B2[j] = iw(w, A2);
           E1[j] = iw(w, D1);
           E2[j] = iw(-w, D2);
         }
       };
-      auto load_node = [&](cd (&K)[3][NB], int n) {
+      auto axial_term = [&](int m, cd (&Bq)[NB]) {   // Bq of member m (axial nodes only)
+        double cq[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) cq[i] = mbf[18 * m + RH_MF_CQ0 + i];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          cd X[6];
+          bin_xi(j, X);
+          cd Aq = mk(0, 0);
+#pragma unroll
+          for (int c = 0; c < 6; ++c) Aq = add(Aq, scl(X[c], cq[c]));
+          Bq[j] = iw(lw[pb + LT * j], Aq);
+        }
+      };
+      // The streaming loop over all nodes carries the two transverse rows only; the axial rows
+      // of the few nodes that need them (ax_node) are summed in a short loop of their own
+      // after it (nothing couples s_q to s_1 and s_2).
+      auto load_node = [&](cd (&K)[2][NB], int n) {
         const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
 #if RH_ABL_A_NOLOAD   // timing ablation: the ring keeps its first nodes (wrong results)
         if (n >= kRingA) return;
@@ -578,77 +673,59 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
-          for (int p = 0; p < 3; ++p) K[p][j] = bld(bK, vb[j], so + (unsigned)p * nw16);
+          for (int p = 0; p < 2; ++p) K[p][j] = bld(bK, vb[j], so + (unsigned)(p + 1) * nw16);
       };
-      // this lane's partial sums over its bins of |s_q|^2, |s_1|^2, |s_2|^2 for one node
-      auto node_sums = [&](const cd (&K)[3][NB], int n, double& s0, double& s1, double& s2) {
+      auto load_axial = [&](cd (&K)[NB], int k) {   // row 0 of the k-th axial node (none past the list)
+        const int n = ax_node(k);
+        if (n >= 0) {   // uniform
+          const unsigned so = (unsigned)n * 3u * nw16;
+#pragma unroll
+          for (int j = 0; j < NB; ++j) K[j] = bld(bK, vb[j], so);
+        } else {
+#pragma unroll
+          for (int j = 0; j < NB; ++j) K[j] = mk(0.0, 0.0);
+        }
+      };
+      // this lane's partial sums over its bins of |s_1|^2, |s_2|^2 for one node
+      auto node_sums = [&](const cd (&K)[2][NB], int n, double& s1, double& s2) {
         const double t = nt[n];
-        s0 = s1 = s2 = 0;
+        s1 = s2 = 0;
 #if RH_ABL_A_NOCOMP   // timing ablation: consume the loads with one add each (wrong results)
 #pragma unroll
-        for (int j = 0; j < NB; ++j) { s0 += K[0][j].r + K[0][j].i; s1 += K[1][j].r + K[1][j].i; s2 += K[2][j].r + K[2][j].i; }
+        for (int j = 0; j < NB; ++j) { s1 += K[0][j].r + K[0][j].i; s2 += K[1][j].r + K[1][j].i; }
         return;
 #endif
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
           const double z = bz[j];
-          const cd sq = sub(scl(K[0][j], z), Bq[j]);
-          const cd sp1 = sub(scl(K[1][j], z), add(B1[j], scl(E1[j], t)));
-          const cd sp2 = sub(scl(K[2][j], z), add(B2[j], scl(E2[j], t)));
-          s0 += abs2(sq);
+          const cd sp1 = sub(scl(K[0][j], z), add(B1[j], scl(E1[j], t)));
+          const cd sp2 = sub(scl(K[1][j], z), add(B2[j], scl(E2[j], t)));
           s1 += abs2(sp1);
           s2 += abs2(sp2);
         }
       };
-      if constexpr (RH_A_BATCH > 0 && !GX) {
-      // Nodes in batches of kB (= the ring depth): the three sums of each node of a batch are
-      // independent chains, and the 3 kB values are reduced over the wave by ONE transposing
-      // butterfly (tbfly16: 17 exchange steps for up to 16 values, against 8 per node for
-      // tbfly3); lanes 0..15 then hold the totals.  The ring slot of node n is refilled with
-      // node n + kB as soon as n is summed.
-      constexpr int kB = RH_A_BATCH > 0 ? RH_A_BATCH : 1;
-      static_assert(3 * kB <= 16, "tbfly16 reduces at most 16 values");
-      cd K[kB][3][NB];
+      // RH_A_QUAD: the sums of a ring round's four nodes reduced together (tbfly8; ring depth 4);
+      // RH_A_PAIR alone: those of nodes 2k and 2k + 1 (tbfly4; even ring depth); with either, the
+      // axial sums of four nodes per tbfly4; otherwise tbfly3 per node, and per three axial nodes
+      constexpr bool kPair = RH_A_PAIR && (kRingA % 2 == 0);
+      constexpr int kAx = kPair ? 4 : 3;   // axial nodes per butterfly
+      const int nA = skip_a ? 0 : nn;   // no node steps when iteration 0's sums came from k_a0_sums
+      // The first kAx axial rows are requested before the ring's, so they arrive behind the
+      // transverse loop; a design with more axial nodes waits once per further kAx of them.
+      cd KQ[kAx][NB];
 #pragma unroll
-      for (int r = 0; r < kB; ++r) load_node(K[r], r);
-      int m = -1, mnext = 0;
-      for (int n = 0; n < nn; n += kB) {
-        double u[16];
-#pragma unroll
-        for (int r = 0; r < kB; ++r) {
-          const int nr = n + r;
-          if (nr < nn) {
-            if (nr == mnext) {   // uniform: entering member m+1 (members are node-contiguous)
-              do { ++m; mnext = mstart[m + 1]; } while (mnext == nr);
-              member_terms(m);
-            }
-            node_sums(K[r], nr, u[3 * r], u[3 * r + 1], u[3 * r + 2]);
-            load_node(K[r], nr + kB);
-          } else {
-            u[3 * r] = u[3 * r + 1] = u[3 * r + 2] = 0.0;
-          }
-        }
-#pragma unroll
-        for (int v = 3 * kB; v < 16; ++v) u[v] = 0.0;
-        const int ln = lane_here();
-        const double tot = tbfly16(u, ln);
-        const int vi = tbfly16_index(ln);
-        if (ln < 16 && vi < 3 * kB && n + vi / 3 < nn) red[((n + vi / 3) * 3 + vi % 3) * LW + wv_s] = tot;
-      }
-      } else {
-      // the three sums of a node are reduced over the wave together (tbfly3); lane k < 3
-      // writes sum k.  The ring slot of node n is refilled with node n + kRingA.
-      cd K[kRingA][3][NB];
+      for (int r = 0; r < kAx; ++r) load_axial(KQ[r], nA > 0 ? r : nn);
+      // The ring slot of node n is refilled with node n + kRingA.
+      cd K[kRingA][2][NB];
 #pragma unroll
       for (int r = 0; r < kRingA; ++r) load_node(K[r], r);
       int m = -1, mnext = 0;
-      const int nA = skip_a ? 0 : nn;   // no node steps when iteration 0's sums came from k_a0_sums
-      // RH_A_PAIR: the sums of nodes 2k and 2k + 1 reduced together (tbfly6; even ring depth)
-      constexpr bool kPair = RH_A_PAIR && (kRingA % 2 == 0);
-      double h0 = 0.0, h1 = 0.0, h2 = 0.0;   // (kPair) the even node's sums
-      // (kPair) the butterfly's lane flags: formed here, live through the node loop only
+      double h1 = 0.0, h2 = 0.0;   // (kPair) the even node's sums
+      constexpr bool kQuad = RH_A_QUAD && kPair && kRingA == 4;
+      [[maybe_unused]] double u8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (kQuad) the sums of a round's nodes
+      // (kPair) the butterfly's lane flags: formed here, live through the node loops only
       // (lane_here is not hoisted out of the iteration loop)
-      const Bfly6 bl = bfly6_lane(kPair ? lane_here() : 0);
+      const Bfly4 bl = bfly4_lane(kPair ? lane_here() : 0);
       for (int n = 0; n < nA; n += kRingA) {
 #pragma unroll
         for (int r = 0; r < kRingA; ++r) {
@@ -658,36 +735,88 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
               do { ++m; mnext = mstart[m + 1]; } while (mnext == nr);
               member_terms(m);
             }
-            double s0, s1, s2;
-            node_sums(K[r], nr, s0, s1, s2);
+            double s1, s2;
+            node_sums(K[r], nr, s1, s2);
             load_node(K[r], nr + kRingA);
+            if constexpr (kQuad) {
+              u8[2 * r] = s1;
+              u8[2 * r + 1] = s2;
+              if (r < 3 && nr + 1 < nA) continue;   // uniform: held for the round's last node
+#pragma unroll
+              for (int q = 2 * r + 2; q < 8; ++q) u8[q] = 0.0;   // a short last round
+              const double tot = tbfly8(u8, bl);
+              if (bl.vi8 >= 0 && (bl.vi8 >> 1) <= r) {
+                double& rr = red[((nr - r + (bl.vi8 >> 1)) * 3 + 1 + (bl.vi8 & 1)) * LW + wv_s];
+                rr = (GX && p > 0) ? rr + tot : tot;
+              }
+              continue;
+            }
             if constexpr (kPair) {
               if ((r & 1) == 0 && nr + 1 < nA) {   // uniform: held for the odd node
-                h0 = s0; h1 = s1; h2 = s2;
+                h1 = s1; h2 = s2;
                 continue;
               }
               const int n0 = (r & 1) ? nr - 1 : nr;   // the pair's even node
-              const double tot = (r & 1) ? tbfly6(h0, h1, h2, s0, s1, s2, bl)
-                                         : tbfly6(s0, s1, s2, 0.0, 0.0, 0.0, bl);   // the last node alone
-              if ((r & 1) ? bl.vi >= 0 : (unsigned)bl.vi < 3u) {
-                double& rr = red[(n0 * 3 + bl.vi) * LW + wv_s];
+              const double tot = (r & 1) ? tbfly4(h1, h2, s1, s2, bl)
+                                         : tbfly4(s1, s2, 0.0, 0.0, bl);   // the last node alone
+              if ((r & 1) ? bl.vi >= 0 : (unsigned)bl.vi < 2u) {
+                double& rr = red[((n0 + (bl.vi >> 1)) * 3 + 1 + (bl.vi & 1)) * LW + wv_s];
                 rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
               }
               continue;
             }
             const int ln = lane_here();
 #if RH_ABL_A_NOBFLY
-            const double tot = s0 + s1 + s2;
+            const double tot = s1 + s2;
 #else
-            const double tot = tbfly3(s0, s1, s2, ln);
+            const double tot = tbfly3(s1, s2, 0.0, ln);
 #endif
-            if (ln < 3) {
-              double& r = red[(nr * 3 + tbfly3_index(ln)) * LW + wv_s];
+            if (ln < 3 && tbfly3_index(ln) < 2) {
+              double& r = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
               r = (GX && p > 0) ? r + tot : tot;   // passes add in pass order
             }
           }
         }
       }
+      // the axial nodes, kAx per butterfly, each with the Bq of its member
+      int ma = 0;
+      for (int k0 = 0; k0 < nA; k0 += kAx) {
+        if (ax_node(k0) < 0) break;   // uniform: the end of the list
+        double q[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int r = 0; r < kAx; ++r) {
+          const int n = ax_node(k0 + r);
+          if (n >= 0) {   // uniform
+            while (n >= __builtin_amdgcn_readfirstlane(mstart[ma + 1])) ++ma;
+            cd Bq[NB];
+            axial_term(ma, Bq);
+            double s0 = 0;
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+              const cd sq = sub(scl(KQ[r][j], bz[j]), Bq[j]);
+              s0 += abs2(sq);
+            }
+            q[r] = s0;
+            load_axial(KQ[r], k0 + r + kAx);
+          }
+        }
+        int vi;
+        double tot;
+        if constexpr (kPair) {
+          tot = tbfly4(q[0], q[1], q[2], q[3], bl);
+          vi = bl.vi;
+        } else {
+          const int ln = lane_here();
+          tot = tbfly3(q[0], q[1], q[2], ln);
+          vi = ln < 3 ? tbfly3_index(ln) : -1;
+        }
+        if (vi >= 0 && k0 + vi < nn) {
+          const int n = ax[12 * (k0 + vi) + 11];
+          if (n >= 0) {
+            double& rr = red[n * 3 * LW + wv_s];
+            rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
+          }
+        }
       }
     }
 #ifdef RH_VARIANTS
@@ -728,6 +857,9 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         for (int w = 0; w < LW; ++w) s += R[w];
         r3[c] = s;
       }
+      // a node that does not need its axial sum has none (phase A wrote no partials for it): an
+      // exact 0, so vq = 0 and Bq = Be = +0, the zeros that its zero coefficients give anyway
+      if (!(ax[12 * n + 10] & 1)) r3[0] = 0.0;
       // sum|vrel_q|^2 = sum|s_q|^2 |q|^2 ; circular: |vrel_p|^2 = |s_1|^2|p1|^2 + |s_2|^2|p2|^2
       auto n2 = [&](int f) { const double a = F(f), b = F(f + 1), c = F(f + 2); return a * a + b * b + c * c; };
       const double qq = n2(RH_NF_QX), pp1 = n2(RH_NF_P1X), pp2 = n2(RH_NF_P2X);
