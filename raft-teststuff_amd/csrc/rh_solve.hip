@@ -8,12 +8,15 @@
 //     The unrelaxed solution is streamed to HBM with non-temporal stores (it is only
 //     consumed after the loop), so it does not evict the wave tables from L2.
 //   * The projected wave table (kproj, the only per-node stream) is read through a buffer
-//     resource (one 32-bit lane offset per bin, node/projection offsets scalar) with a
-//     3-slot register ring: node n+2 is in flight while node n is reduced.
+//     resource (one 32-bit lane offset per bin, node/projection offsets scalar) with a register
+//     ring of kRingA1 / kRingC nodes (the two transverse rows of each).  The node loops run whole
+//     ring rounds with no load under a branch, so that every wait leaves the other slots' loads
+//     outstanding (tools/isa_check.py gates it).
 //   * Per-node bin sums: a 6-step DPP wave reduction (VALU only, no LDS or SGPR traffic),
 //     one partial per wave, summed in wave order.  Fixed order, so results are deterministic.
 //   * The axial row of a node (projection 0) is read only where the node has axial side drag or
-//     end drag; elsewhere it would meet coefficients that are exact zeros (same bits without it).
+//     end drag, in short loops of their own after the node loops of phases A and C; elsewhere it
+//     would meet coefficients that are exact zeros.
 #include "rh_common.h"
 #ifdef RH_VARIANTS
 #include "../../tools/ubench/variants_src/rh_a0_common.h"   // k_a0_sums sums (rh_set_a0)
@@ -64,10 +67,14 @@ constexpr int kRingC = RH_RING_C; // ... of phase C (one bin per pass: less work
 #ifndef RH_A_PAIR
 #define RH_A_PAIR 1                   // 1: phase-A sums of two nodes per butterfly (tbfly4)
 #endif
-#ifndef RH_C_AXIAL
-#define RH_C_AXIAL 2                  // phase C's axial row of a node that does not need it: 0: loaded; 1: through a closed
-                                      // descriptor; 2: not loaded (uniform branch); 3: nor accumulated (A/B)
-#endif
+constexpr int kAxC = 4;               // axial wave-table rows phase C holds at a time (its own path, beside the ring)
+// Ghost nodes: the node loops of phases A and C run whole ring rounds, so no slot of a round is
+// under a tail guard (a guarded slot is a merge point at which hipcc stops counting the ring's loads
+// and waits for all of them).  Nodes nn .. of the last round load the last node's rows
+// again and meet zero coefficients in phase C (exact +0) or write no partial in phase A.  The
+// node-indexed LDS tables that the loops read carry one zero row, row nn, for all of them (56
+// bytes: the C4 kernel's four workgroups per CU have about 300 bytes of LDS to spare).
+constexpr int kGhost = 1;
 #ifndef RH_A_QUAD
 #define RH_A_QUAD 1                   // 1: phase-A transverse sums of four nodes per butterfly (tbfly8; ring depth 4)
 #endif
@@ -275,8 +282,8 @@ __host__ __device__ inline size_t solve_lds_smem(int nn, int nm, int NB, int LT 
                            + (size_t)(ser && nn * 3 * LW < 27 ? 27 : nn * 3 * LW)   // per-wave node sums (SER: >= 27 entries)
                            + (ser ? (size_t)0 : (size_t)nn * 36)   // per-node B_drag contributions
                            + (size_t)nn * 9           // Bmat
-                           + (size_t)nn * 6           // member-factored drag coefficients (stride 6: 16-B rows)
-                           + (size_t)nn               // node axial coordinate t
+                           + (size_t)(nn + kGhost) * 6   // member-factored drag coefficients (stride 6: 16-B rows; ghost row)
+                           + (size_t)(nn + kGhost)    // node axial coordinate t
                            + (size_t)nm * 18          // member cq, c1, c2
                            + (size_t)2 * LT * NB * NP   // w and zeta per (padded) bin
                            + 36 + 108 + LW * 6 + 36  // B_drag, M|B|C image, std partials, B_lin+B_drag
@@ -321,10 +328,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   const int head = a.c.head[ic];
   const size_t c6 = (size_t)ic * 6 * nw;
   const Buf bK = mkbuf(d.kproj + (size_t)head * nn * 3 * nw, (unsigned)nn * 3u * nw16);
-  // (RH_C_AXIAL == 1, A/B only) the same table with the bounds closed when `on` is false
-  // (uniform): every lane is then out of range and the load returns 0 without traffic, still one
-  // vector-memory operation; measured slower than a branch around the load
-  [[maybe_unused]] auto bK_if = [&](bool on) { return mkbuf(d.kproj + (size_t)head * nn * 3 * nw, on ? (unsigned)nn * 3u * nw16 : 0u); };
   const Buf bFe = mkbuf(d.finer + (size_t)head * 6 * nw, 6u * nw16);
   const bool has_fx = a.c.fext != nullptr;
   const Buf bFx = mkbuf(has_fx ? a.c.fext + c6 : nullptr, has_fx ? 6u * nw16 : 0u);
@@ -352,16 +355,16 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   // the loops, come first, member- / node-major with 16-byte rows (a member's 18 factors are
   // 9 ds_read_b128 at one base address instead of 18 scattered reads at nm-strided addresses).
   double* mbf = smem + (GX ? 0 : 12 * NWP);        // [nm][18] cq, c1, c2
-  double* al = mbf + 18 * nm;                      // [nn][6] (5 used)
-  double* red = al + 6 * nn;                       // [nn*3][LW]
+  double* al = mbf + 18 * nm;                      // [nn + kGhost][6] (5 used; the ghost row stays 0)
+  double* red = al + 6 * (nn + kGhost);            // [nn*3][LW]
   double* bm = red + (SER && nn * 3 * LW < 27 ? 27 : nn * 3 * LW);   // [nn][9]
   double* bd = bm + nn * 9;                        // [36]
   double* mbc = bd + 36;                           // [108] M, B_lin, C
   double* sred = mbc + 108;                        // [LW][6]
   double* bsum = sred + LW * 6;                   // [36] B_lin + B_drag of this iteration
   double* bdn = bsum + 36;                         // [36][nn] (not with SER)
-  double* nt = bdn + (SER ? 0 : 36 * nn);          // [nn]
-  double* lw = nt + nn;                            // [NP NWP] w per bin (pad bins: w[nw-1])
+  double* nt = bdn + (SER ? 0 : 36 * nn);          // [nn + kGhost] (ghost entry 0)
+  double* lw = nt + nn + kGhost;                   // [NP NWP] w per bin (pad bins: w[nw-1])
   double* lz = lw + NP * NWP;                      // [NP NWP] zeta per bin (pad bins: 0)
   double* mred = lz + NP * NWP;                    // [LW] per-wave max of tolCheck
   int* mstart = reinterpret_cast<int*>(mred + LW);  // [nm+1]
@@ -369,11 +372,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   // end drag, AQ CDQ != 0 or AEND CDEND != 0 (node_bmat_f); for every other node the row enters
   // the result only through coefficients that are exact zeros (Cd_q defaults to 0 and end areas
   // are non-zero only at member ends and diameter steps: 4 of 53 nodes of C2).  Kept in the
-  // spare sixth double of the node's `al` row as two ints: [0] the flags of nodes n .. n + 31
-  // (bit 0: the node's own; one read serves a whole round of a prefetch ring), [1] entry k = n of
-  // the compact, node-ordered list of the axial nodes (-1 past its end).
+  // spare sixth double of the node's `al` row as two ints: [0] the node's flag (phase B), [1] entry
+  // k = n of the compact, node-ordered list of the axial nodes (-1 past its end), which the axial
+  // loops of phases A and C walk.
   int* ax = reinterpret_cast<int*>(al);
-  auto ax_win = [&](int n) { return n < nn ? __builtin_amdgcn_readfirstlane(ax[12 * n + 10]) : 0; };   // n uniform
   auto ax_node = [&](int k) { return k < nn ? __builtin_amdgcn_readfirstlane(ax[12 * k + 11]) : -1; };   // k uniform
   int* sflag = mstart + nm + 1;                      // [2] vote words of even / odd iterations,
                                                      // [2]: it + 1 once a test of iteration it failed,
@@ -386,7 +388,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     ax[12 * n + 10] = (a.all_axial || aq * cdq != 0.0 || ae * cde != 0.0) ? 1 : 0;
   }
   for (int e = tid; e < 18 * nm; e += LT) mbf[e] = d.memb[(e % 18) * nm + e / 18];   // RH_MF_CQ0..C20: fields 0..17
-  for (int e = tid; e <= nm; e += LT) mstart[e] = d.mstart[e];
+  // (the last member's end is never met by a node index: ghost nodes open or close no member)
+  for (int e = tid; e <= nm; e += LT) mstart[e] = e < nm ? d.mstart[e] : INT_MAX;
+  for (int e = tid; e < 6 * kGhost; e += LT) al[6 * nn + e] = 0.0;
+  for (int e = tid; e < kGhost; e += LT) nt[nn + e] = 0.0;
   if (tid < 5) sflag[tid] = 0;
   const int it0 = resume ? stop_iter : a.c.first_iter;
   // Iteration 0's phase-A sums formed for the whole batch by k_a0_sums (rh_a0.hip): their
@@ -469,14 +474,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     if (n >= nq) ax[12 * n + 11] = -1;
   }
   __syncthreads();
-  for (int n0 = 0; n0 < nn; n0 += LT) {   // the flag windows (a round reads only words not yet rewritten)
-    const int n = n0 + tid;
-    int w = 0;
-    for (int i = 0; i < 32; ++i)
-      if (n + i < nn) w |= (ax[12 * (n + i) + 10] & 1) << i;
-    __syncthreads();
-    if (n < nn) ax[12 * n + 10] = w;
-  }
   __syncthreads();
   PROF_T(tp1);
   PROF_ADD(0, tp1 - tp0);
@@ -496,76 +493,110 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     for (int c = 0; c < 6; ++c) F[c] = mk(0, 0);
     {
       cd SQ = mk(0, 0), S1 = mk(0, 0), S2 = mk(0, 0), T1 = mk(0, 0), T2 = mk(0, 0);
-      auto load1 = [&](cd (&K)[3], int n, bool axial) {
+      auto load1 = [&](cd (&K)[2], int n) {
         const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
 #if RH_ABL_C_NOLOAD
         if (n >= kRingC) return;
 #endif
-        // the axial row only where it is needed (uniform branch; two-bin kernels): elsewhere
-        // K[0] = 0 meets A[0] = +0, and SQ (which starts at +0) keeps its bits
-#if RH_C_AXIAL == 1
-        K[0] = bld(NB > 1 ? bK_if(axial) : bK, vj, so);
-#elif RH_C_AXIAL >= 2
-        if (NB == 1 || axial) K[0] = bld(bK, vj, so);
-        else K[0] = mk(0.0, 0.0);
-#else
-        K[0] = bld(bK, vj, so);
-#endif
 #pragma unroll
-        for (int p = 1; p < 3; ++p) K[p] = bld(bK, vj, so + (unsigned)p * nw16);
+        for (int p = 0; p < 2; ++p) K[p] = bld(bK, vj, so + (unsigned)(p + 1) * nw16);
+      };
+      auto load_axial = [&](cd& Kq, int k) {   // row 0 of the k-th axial node (none past the list)
+        const int n = ax_node(k);
+        if (n >= 0) Kq = bld(bK, vj, (unsigned)n * 3u * nw16);   // uniform
+        else Kq = mk(0.0, 0.0);
       };
       int m = 0, mnext = nn > 0 ? mstart[1] : 0;
       auto fold = [&]() {   // close member m: F += sum of its nodes (as drag_exc_members)
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-          const double cq = mbf[18 * m + RH_MF_CQ0 + i], c1 = mbf[18 * m + RH_MF_C10 + i],
-                       c2 = mbf[18 * m + RH_MF_C20 + i];
-          F[i] = add(F[i], add(add(scl(SQ, cq), scl(S1, c1)), scl(S2, c2)));
+          const double c1 = mbf[18 * m + RH_MF_C10 + i], c2 = mbf[18 * m + RH_MF_C20 + i];
+          F[i] = add(F[i], add(scl(S1, c1), scl(S2, c2)));
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           const double p1 = mbf[18 * m + RH_MF_C10 + i], p2 = mbf[18 * m + RH_MF_C20 + i];
           F[3 + i] = add(F[3 + i], sub(scl(T1, p2), scl(T2, p1)));
         }
-        SQ = S1 = S2 = T1 = T2 = mk(0, 0);
+        S1 = S2 = T1 = T2 = mk(0, 0);
       };
-      auto step = [&](cd (&K)[3], int n, [[maybe_unused]] bool axial, bool next_axial) {
+      // The node ring carries the two transverse rows of every node.  The axial rows of the few
+      // nodes that need them (ax_node) are summed in a short loop of their own after it, as in phase
+      // A: a load under a branch inside the node loop, even a uniform one, is a merge point at which
+      // hipcc stops counting the ring's loads and waits for nearly all of them.  The
+      // first kAxC axial rows are requested before the ring's, so they have arrived behind the node loop.
+      // (Both are requested in ring order, each slot scheduled by itself: the waits of the first round
+      // are counted from here, and hipcc takes the smaller of this count and the steady state's.)
+      cd KQ[kAxC];
+#pragma unroll
+      for (int r = 0; r < kAxC; ++r) load_axial(KQ[r], nn > 0 ? r : nn);
+      __builtin_amdgcn_sched_barrier(0);
+      cd K[kRingC][2];
+#pragma unroll
+      for (int r = 0; r < kRingC; ++r) {
+        load1(K[r], r);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // node n's coefficient row is read while node n - 1 is consumed (ghost nodes: row nn, zeros)
+      double A1 = al[1], A2 = al[2], A3 = al[3], A4 = al[4];
+      auto step = [&](cd (&K)[2], int n) {
         while (n == mnext) {   // uniform: member m ended before node n
           fold();
           ++m;
           mnext = mstart[m + 1];
         }
-        const double* A = al + 6 * n;
-        const double A0 = A[0], A1 = A[1], A2 = A[2], A3 = A[3], A4 = A[4];
+        const double a1 = A1, a2 = A2, a3 = A3, a4 = A4;
+        {
+          const double* A = al + 6 * (n + 1 < nn ? n + 1 : nn);
+          A1 = A[1]; A2 = A[2]; A3 = A[3]; A4 = A[4];
+        }
 #if RH_ABL_C_NOCOMP
-        SQ = add(SQ, K[0]); S1 = add(S1, K[1]); S2 = add(S2, K[2]);
-        load1(K, n + kRingC, next_axial);
+        S1 = add(S1, K[0]); S2 = add(S2, K[1]);
+        load1(K, n + kRingC);
         return;
 #endif
-#if RH_C_AXIAL == 3
-        if (NB == 1 || axial)   // uniform
-#endif
-        SQ = add(SQ, scl(K[0], A0));
-        S1 = add(S1, scl(K[1], A1));
-        S2 = add(S2, scl(K[2], A2));
-        T1 = add(T1, scl(K[1], A3));
-        T2 = add(T2, scl(K[2], A4));
-        load1(K, n + kRingC, next_axial);
+        S1 = add(S1, scl(K[0], a1));
+        S2 = add(S2, scl(K[1], a2));
+        T1 = add(T1, scl(K[0], a3));
+        T2 = add(T2, scl(K[1], a4));
+        __builtin_amdgcn_sched_barrier(0);   // consumed before the refill is issued (as in phase A)
+        load1(K, n + kRingC);
+        __builtin_amdgcn_sched_barrier(0);
       };
-      cd K[kRingC][3];
-      static_assert(kRingC <= 32, "one flag window per ring round");
-      const int w0 = ax_win(0);
+#pragma unroll 1
+      for (int n = 0; n < nn; n += kRingC) {   // whole rounds: the last one ends in ghost nodes
 #pragma unroll
-      for (int r = 0; r < kRingC; ++r) load1(K[r], r, ((w0 >> r) & 1) != 0);
-      int wc = w0;   // the flags of the round's own nodes
-      for (int n = 0; n < nn; n += kRingC) {
-        const int w = ax_win(n + kRingC);   // ... and of the nodes it requests
-#pragma unroll
-        for (int r = 0; r < kRingC; ++r)
-          if (n + r < nn) step(K[r], n + r, ((wc >> r) & 1) != 0, ((w >> r) & 1) != 0);
-        wc = w;
+        for (int r = 0; r < kRingC; ++r) step(K[r], n + r);
       }
       if (nn > 0) fold();
+      // The axial nodes in node order: SQ receives the terms of one member's axial nodes, and the
+      // member's sum is added to F where its last axial node has been taken: F += SQ cq after the
+      // members' transverse sums, not (SQ cq + S1 c1) + S2 c2 inside them.
+      {
+        int ma = 0, mq = -1;   // the member of the node, and of the terms SQ holds
+        auto flush = [&]() {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) F[i] = add(F[i], scl(SQ, mbf[18 * mq + RH_MF_CQ0 + i]));
+          SQ = mk(0, 0);
+        };
+        for (int k0 = 0; k0 < nn; k0 += kAxC) {
+          if (ax_node(k0) < 0) break;   // uniform: the end of the list
+#pragma unroll
+          for (int r = 0; r < kAxC; ++r) {
+            const int n = ax_node(k0 + r);
+            if (n >= 0) {   // uniform
+              while (n >= __builtin_amdgcn_readfirstlane(mstart[ma + 1])) ++ma;
+              if (ma != mq) {
+                if (mq >= 0) flush();
+                mq = ma;
+              }
+              SQ = add(SQ, scl(KQ[r], al[6 * n]));
+              load_axial(KQ[r], k0 + r + kAxC);
+            }
+          }
+        }
+        if (mq >= 0) flush();
+      }
     }
     const double z = lz[bj];
 #pragma unroll
@@ -687,8 +718,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         }
       };
       // this lane's partial sums over its bins of |s_1|^2, |s_2|^2 for one node
-      auto node_sums = [&](const cd (&K)[2][NB], int n, double& s1, double& s2) {
-        const double t = nt[n];
+      auto node_sums = [&](const cd (&K)[2][NB], double t, double& s1, double& s2) {
         s1 = s2 = 0;
 #if RH_ABL_A_NOCOMP   // timing ablation: consume the loads with one add each (wrong results)
 #pragma unroll
@@ -718,7 +748,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       // The ring slot of node n is refilled with node n + kRingA.
       cd K[kRingA][2][NB];
 #pragma unroll
-      for (int r = 0; r < kRingA; ++r) load_node(K[r], r);
+      for (int r = 0; r < kRingA; ++r) {   // in ring order (see phase C)
+        load_node(K[r], r);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       int m = -1, mnext = 0;
       double h1 = 0.0, h2 = 0.0;   // (kPair) the even node's sums
       constexpr bool kQuad = RH_A_QUAD && kPair && kRingA == 4;
@@ -726,54 +759,58 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       // (kPair) the butterfly's lane flags: formed here, live through the node loops only
       // (lane_here is not hoisted out of the iteration loop)
       const Bfly4 bl = bfly4_lane(kPair ? lane_here() : 0);
+      // Whole ring rounds: the last one ends in ghost nodes (the last node's rows again), whose sums
+      // are reduced like any other's and written nowhere.  node n's t is read a node ahead.
+      double tn = nt[0];
+#pragma unroll 1
       for (int n = 0; n < nA; n += kRingA) {
 #pragma unroll
         for (int r = 0; r < kRingA; ++r) {
           const int nr = n + r;
-          if (nr < nA) {
-            if (nr == mnext) {   // uniform: entering member m+1 (members are node-contiguous)
-              do { ++m; mnext = mstart[m + 1]; } while (mnext == nr);
-              member_terms(m);
-            }
-            double s1, s2;
-            node_sums(K[r], nr, s1, s2);
-            load_node(K[r], nr + kRingA);
-            if constexpr (kQuad) {
-              u8[2 * r] = s1;
-              u8[2 * r + 1] = s2;
-              if (r < 3 && nr + 1 < nA) continue;   // uniform: held for the round's last node
-#pragma unroll
-              for (int q = 2 * r + 2; q < 8; ++q) u8[q] = 0.0;   // a short last round
+          if (nr == mnext) {   // uniform: entering member m+1 (members are node-contiguous)
+            do { ++m; mnext = mstart[m + 1]; } while (mnext == nr);
+            member_terms(m);
+          }
+          double s1, s2;
+          node_sums(K[r], tn, s1, s2);
+          // The slot's rows are consumed here, before its refill is issued.  Without the member
+          // boundaries' merge points between them nothing else holds the sums in place: they are used
+          // only by the round's butterfly, the compiler sinks them down to it, every slot's old rows
+          // stay live beside their refills, and the ring spills (the opaque statement pins them).
+          asm volatile("" : "+v"(s1), "+v"(s2));
+          tn = nt[nr + 1 < nn ? nr + 1 : nn];
+          load_node(K[r], nr + kRingA);
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (kQuad) {
+            u8[2 * r] = s1;
+            u8[2 * r + 1] = s2;
+            if (r == kRingA - 1) {   // (folded by the unrolling)
               const double tot = tbfly8(u8, bl);
-              if (bl.vi8 >= 0 && (bl.vi8 >> 1) <= r) {
-                double& rr = red[((nr - r + (bl.vi8 >> 1)) * 3 + 1 + (bl.vi8 & 1)) * LW + wv_s];
+              if (bl.vi8 >= 0 && n + (bl.vi8 >> 1) < nA) {
+                double& rr = red[((n + (bl.vi8 >> 1)) * 3 + 1 + (bl.vi8 & 1)) * LW + wv_s];
                 rr = (GX && p > 0) ? rr + tot : tot;
               }
-              continue;
             }
-            if constexpr (kPair) {
-              if ((r & 1) == 0 && nr + 1 < nA) {   // uniform: held for the odd node
-                h1 = s1; h2 = s2;
-                continue;
-              }
-              const int n0 = (r & 1) ? nr - 1 : nr;   // the pair's even node
-              const double tot = (r & 1) ? tbfly4(h1, h2, s1, s2, bl)
-                                         : tbfly4(s1, s2, 0.0, 0.0, bl);   // the last node alone
-              if ((r & 1) ? bl.vi >= 0 : (unsigned)bl.vi < 2u) {
-                double& rr = red[((n0 + (bl.vi >> 1)) * 3 + 1 + (bl.vi & 1)) * LW + wv_s];
+          } else if constexpr (kPair) {
+            if ((r & 1) == 0) {   // held for the odd node
+              h1 = s1; h2 = s2;
+            } else {
+              const double tot = tbfly4(h1, h2, s1, s2, bl);
+              if (bl.vi >= 0 && nr - 1 + (bl.vi >> 1) < nA) {
+                double& rr = red[((nr - 1 + (bl.vi >> 1)) * 3 + 1 + (bl.vi & 1)) * LW + wv_s];
                 rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
               }
-              continue;
             }
+          } else {
             const int ln = lane_here();
 #if RH_ABL_A_NOBFLY
             const double tot = s1 + s2;
 #else
             const double tot = tbfly3(s1, s2, 0.0, ln);
 #endif
-            if (ln < 3 && tbfly3_index(ln) < 2) {
-              double& r = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
-              r = (GX && p > 0) ? r + tot : tot;   // passes add in pass order
+            if (ln < 3 && tbfly3_index(ln) < 2 && nr < nA) {
+              double& rr = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
+              rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
             }
           }
         }

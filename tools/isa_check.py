@@ -11,7 +11,11 @@ checks every kernel:
     while one of its loads is outstanding (in_flight_scratch): a spill reload there shares
     `vmcnt` with the wave-table prefetch ring and drains it every node (k_solve_pair's first
     build lost 4x in phase A to exactly this) -> FAIL;
-  * scratch instructions elsewhere (prologue, solve, member boundaries) are counted and reported.
+  * scratch instructions elsewhere (prologue, solve, member boundaries) are counted and reported;
+  * the depth the prefetch rings really keep: per streaming loop, the loads issued per trip and
+    min_outstanding, the smallest vmcnt(N) waited for with loads of the loop in flight (`rings=`);
+    in the two benched fixed points the phase-A and phase-C node loops must keep
+    (ring depth - 1) x loads per slot outstanding (`ringA=`, `ringC=`) -> FAIL below that.
 Loops are found from the branch structure: a branch to a label that precedes it closes a loop
 [label, branch]; a loop that contains no other loop is innermost; it streams if it holds a
 buffer_load / global_load.
@@ -130,6 +134,55 @@ def in_flight_scratch(body, a, b):
     return walk(carried)[1]
 
 
+def ring_depth(body, a, b):
+    """(loads per trip, min_outstanding) of the streaming loop [a, b]: the vector-memory loads it issues in
+    one trip, and the smallest N of any `s_waitcnt vmcnt(N)` reached inside it while loads are in flight
+    (the counter modelled as in in_flight_scratch, with the back edge's loads carried to the head).  A
+    prefetch ring D slots deep that really stays full never waits below (D - 1) x loads per slot; a loop
+    that drains its ring somewhere shows 0.  None: the loop never waits with a load in flight."""
+    def walk(carried):
+        out, low = carried, None
+        for i in range(a, b + 1):
+            ln = body[i]
+            m = VMCNT.match(ln)
+            if m:
+                n = int(m.group(1))
+                if out > 0:
+                    low = n if low is None else min(low, n)
+                out = min(out, n)
+            elif SCRATCH_LOAD.match(ln) or STREAM.match(ln):
+                out += 1
+        return out, low
+    loads = sum(1 for i in range(a, b + 1) if STREAM.match(body[i]))
+    carried, _ = walk(0)
+    return loads, walk(carried)[1]
+
+
+def ring_depths():
+    """kRingA1 and kRingC as rh_solve.hip defines them."""
+    with open(os.path.join(G.CSRC, "rh_solve.hip")) as fh:
+        src = fh.read()
+    return tuple(int(re.search(r"#define %s (\d+)" % k, src).group(1)) for k in ("RH_RING_A", "RH_RING_C"))
+
+
+# The benched fixed points (C2, C4; two bins per thread), whose two main node loops are gated: the
+# phase-A transverse ring (kRingA1 slots of 2 rows x 2 bins) and the phase-C node loop (kRingC slots
+# of 2 rows, one bin per pass) must keep all slots but the one being consumed in flight at every wait.
+RING_GATED = ("k_solve_lds<2, 512, false, 1>", "k_solve_lds<2, 128, true, 1>")
+
+
+def ring_gate(rings):
+    """[(name, loads, min_outstanding, needed)] of the two gated loops among a kernel's streaming loops,
+    picked by their loads per trip (the short axial loops issue fewer)."""
+    ra, rc = ring_depths()
+    out = []
+    for name, per_trip, per_slot, depth in (("A", ra * 4, 4, ra), ("C", rc * 2, 2, rc)):
+        # (the compiler may emit a loop more than once: every copy counts, the worst one is reported)
+        hit = [m for l, m in rings if l == per_trip]
+        out.append((name, per_trip, None if not hit or None in hit else min(hit), (depth - 1) * per_slot))
+    return out
+
+
 def analyse(body):
     labels = {}
     for i, ln in enumerate(body):
@@ -143,12 +196,16 @@ def analyse(body):
             loops.append((labels[m.group(2)], i))
     inner = [l for l in loops if not any(o != l and l[0] <= o[0] and o[1] <= l[1] for o in loops)]
     inner = [(a, b) for a, b in inner if any(STREAM.match(body[i]) for i in range(a, b + 1))]
+    # for the ring measure a node loop counts even where it holds load-free loops of its own (the
+    # member-boundary `while`s): every loop that issues loads and holds no other loop that does
+    stream = sorted({l for l in loops if any(STREAM.match(body[i]) for i in range(l[0], l[1] + 1))})
+    ring_loops = [l for l in stream if not any(o != l and l[0] <= o[0] and o[1] <= l[1] for o in stream)]
     dyn = [ln.strip() for ln in body if DYN_INDEX.match(ln)]
     scr = [i for i, ln in enumerate(body) if SCRATCH.match(ln)]
     scr_inner = [i for a, b in inner for i in in_flight_scratch(body, a, b)]
     scr_loop = [i for a, b in inner for i in range(a, b + 1) if SCRATCH.match(body[i])]
     return {"dyn": dyn, "scratch": len(scr), "scratch_inner": len(scr_inner), "scratch_loop": len(scr_loop),
-            "loops": len(loops), "inner": len(inner)}
+            "loops": len(loops), "inner": len(inner), "rings": [ring_depth(body, a, b) for a, b in ring_loops]}
 
 
 def demangle(n):
@@ -162,6 +219,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm")
     ap.add_argument("--out")
+    ap.add_argument("--no-ring-gate", action="store_true", help="report the ring depths without gating them")
     ap.add_argument("-D", action="append", default=[], help="extra preprocessor define (A/B variants)")
     args = ap.parse_args()
     path = args.asm or compile_asm(["-D" + d for d in args.D])
@@ -186,11 +244,20 @@ def main():
             else:
                 verdict = (f"ok (ratchet: {r['scratch_inner']} <= {allow} with loads in flight, {r['scratch_loop']} <= "
                            f"{allow_loop} anywhere in streaming loops, general path)")
+        # every streaming loop in program order as loads per trip / min_outstanding ("-": never waits
+        # with a load in flight)
+        rings = " rings=" + ",".join(f"{l}/{'-' if m is None else m}" for l, m in r["rings"])
+        if any(k in dn for k in RING_GATED):
+            for ph, per_trip, low, need in ring_gate(r["rings"]):
+                rings += f" ring{ph}={'?' if low is None else low}>={need}"
+                if (low is None or low < need) and not args.no_ring_gate and not verdict.startswith("FAIL"):
+                    verdict = (f"FAIL phase-{ph} ring ({per_trip} loads per trip): min_outstanding "
+                               f"{'not found' if low is None else low} < {need}")
         if verdict.startswith("FAIL"):
             fails.append(dn)
         rows.append(f"{dn:70s} hot={int(hot)} loops={r['loops']:3d} inner={r['inner']:3d} "
                     f"scratch={r['scratch']:4d} in_flight={r['scratch_inner']:3d} in_loops={r['scratch_loop']:3d}  "
-                    f"{verdict}")
+                    f"{verdict}{rings}")
     text = "# tools/isa_check.py: gfx950 device assembly of " + " + ".join(u for u, _ in G.UNITS) + "\n" + "\n".join(rows) + "\n"
     text += f"# {len(ks)} kernels, {len(fails)} failing\n"
     print(text)
