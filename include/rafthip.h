@@ -270,6 +270,55 @@ typedef struct {
 int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* designs, const rh_bem_design* designs_dev,
                             rh_stream stream);
 
+/* ---- quasi-static mooring and mean offsets (csrc/rh_moor.h, rh_moor.hip) ----
+ * The device form of raft/mooring.py for ONE coupled body whose lines each join one fixed point
+ * and one body-attached point (no free points, no current on the lines, W >= 0), and of
+ * Model.solveStatics' Newton on it.  One lane per (pose, line); the lines of a pose sit in
+ * adjacent lanes of a group of the next power of two >= the largest nline, at most 64. */
+enum rh_moor_line_field {
+  RH_ML_FX, RH_ML_FY, RH_ML_FZ, /* fixed end, global [m] */
+  RH_ML_AX, RH_ML_AY, RH_ML_AZ, /* attached end, body frame [m] */
+  RH_ML_L,                      /* unstretched length [m] */
+  RH_ML_EA,                     /* axial stiffness [N] */
+  RH_ML_W,                      /* wet weight per length [N/m], >= 0 */
+  RH_ML_END,                    /* which end of the line is the attached one: 0 = A, 1 = B */
+  RH_ML_COUNT
+};
+#define RH_MOOR_MAX_LINES 64
+
+typedef struct {
+  int nline, pad_;
+  double depth, tol;  /* MooringSystem.depth, cat_tol */
+  const double* line; /* device [RH_ML_COUNT][nline], struct of arrays */
+} rh_moor_system;
+
+/* per-pose / per-case status written by the two calls below (0 = fine; a pose reports the largest
+ * of its lines): 1 catenary XF < 0, 2 L <= 0, 3 EA <= 0, 4 catenary not converged, 5 Newton not
+ * converged within 20 evaluations, 6 singular 6 x 6 step matrix, 7 sys_idx out of range. */
+
+/* Forces, analytic stiffness and end tensions (optionally the tension Jacobian) of npose poses.
+ * sys: HOST array of nsys records, validated here; sys_dev: the same records in device memory.
+ * sys_idx: device [npose] or NULL (every pose uses system 0).  r6: device [npose][6].
+ * nl_max = the largest nline of sys[0..nsys).  warm: device [npose][nl_max][2] (HF, VF) of each
+ * line, read as the catenary's start (0 = cold) and overwritten with its solution, or NULL
+ * (cold, not written).  F [npose][6] = body_forces(lines_only=True); K [npose][36] =
+ * coupled_stiffness_analytic(); T [npose][2 nl_max]: TA of line l in column l, TB in column
+ * nl_max + l; J [npose][2 nl_max][6] or NULL: dT/dX by central differences (0.1 m, 0.1 rad),
+ * every perturbed solve started from the pose's own solution, rows as T.  Columns of lines a
+ * system does not have are written as zeros.  status: device [npose]. */
+int rh_moor_eval(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int npose,
+                 const int* sys_idx, const double* r6, double* warm, double* F, double* K, double* T, double* J,
+                 int* status, rh_stream stream);
+
+/* Mean offsets of ncase cases: Model.solveStatics (statics_mod 0, forcing_mod 0) of one FOWT with
+ * its own mooring system.  X_ref [ncase][6]; K_hs [ncase][36] = C_struc + C_hydro; F_const
+ * [ncase][6] = W_struc + W_hydro + F_env; warm0 [ncase][nl_max][2] the catenary state at X_ref
+ * or NULL (cold).  Out: X [ncase][6] (the last evaluated pose), warm [ncase][nl_max][2] (the line
+ * solutions at X), iters [ncase] (evaluations, len(Model.Xs2)), status [ncase]. */
+int rh_statics_solve(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int ncase,
+                     const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
+                     const double* warm0, double* X, double* warm, int* iters, int* status, rh_stream stream);
+
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
  * (raft/raft_model.py:877-1013) including FOWT.calcHydroLinearization (raft/raft_fowt.py:

@@ -441,6 +441,10 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
   return RH_OK;
 }
 
+}  // extern "C" (rh_moor.h has templates; the two calls take their linkage from rafthip.h)
+#include "rh_moor.hip"   // k_moor_eval, k_statics_solve + rh_moor_eval, rh_statics_solve (uses fail / RH_HIP above)
+extern "C" {
+
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,
                    const rh_solve_out* out, rh_stream stream) {
   if (!ctx || !designs || !cases || !out) return fail(RH_EINVAL, "rh_solve_cases: null argument");

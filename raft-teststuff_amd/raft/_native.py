@@ -65,6 +65,20 @@ class RhBemDesign(ctypes.Structure):
                 ("k", _p), ("headings_deg", _p), ("X", _p), ("beta", _p), ("finer", _p), ("fbem", _p), ("fexc", _p)]
 
 
+class RhMoorSystem(ctypes.Structure):
+    _fields_ = [("nline", ctypes.c_int), ("pad_", ctypes.c_int), ("depth", ctypes.c_double), ("tol", ctypes.c_double),
+                ("line", _p)]
+
+
+# line-table field order (enum rh_moor_line_field)
+MOOR_LINE_FIELDS = ["FX", "FY", "FZ", "AX", "AY", "AZ", "L", "EA", "W", "END"]
+ML_COUNT = len(MOOR_LINE_FIELDS)
+MOOR_MAX_LINES = 64
+MOOR_STATUS = {0: "ok", 1: "catenary: XF < 0", 2: "catenary: L <= 0", 3: "catenary: EA <= 0",
+               4: "catenary did not converge", 5: "statics Newton did not converge", 6: "singular step matrix",
+               7: "system index out of range"}
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -96,6 +110,10 @@ def lib():
                 "rh_bem_excitation": [_p, ctypes.c_int, _p, ctypes.c_int, _p, _p, ctypes.c_int, _p, ctypes.c_double,
                                       ctypes.c_double, ctypes.c_double, _p, _p, _p, _p],
                 "rh_bem_excitation_batch": [_p, ctypes.c_int, ctypes.POINTER(RhBemDesign), _p, _p],
+                "rh_moor_eval": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p,
+                                 _p, _p, _p],
+                "rh_statics_solve": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,
+                                     _p, _p, _p, _p, _p, _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,

@@ -7,8 +7,10 @@ Drop-in for the reference entry points on the hot path (raft/raft_model.py):
 plus the batched form the reference does not have:
   Model.analyzeCasesBatch(cases)  every case in ONE device call (one workgroup per case).
 
-Mean offsets (solveStatics: MoorPy equilibrium) are not solved: the platform stays at its
-reference position, exactly the state the goldens are generated in.
+By default the batch does not solve mean offsets (solveStatics: MoorPy equilibrium): the platform
+stays at its reference position, exactly the state the goldens are generated in.
+  Model.solveStaticsBatch(cases)  the mean offsets of every case on the device (csrc/rh_moor.hip);
+  analyzeCasesBatch(cases, statics=True) solves each case at its own offset pose, as analyzeCases does.
 """
 import ctypes
 
@@ -18,7 +20,7 @@ from . import _native as N
 from .fowt import FOWT, mooring_outputs
 from .hydro_math import DEG2RAD, get_from_dict, wave_numbers
 from .second_order import file_qtf_forces, qtf_index_error, solve_batch_2nd
-from .solver import CaseSet, solve_batch
+from .solver import BatchResult, CaseSet, solve_batch
 
 
 class CaseMB:
@@ -347,6 +349,127 @@ class Model:
                       f"{fowt.Xi0[1]: .2f},  and heave = {fowt.Xi0[2]: .2f} m")
         return X
 
+    def _statics_batch_inputs(self, cases, F_extra=None):
+        """The host side of solveStaticsBatch: the device mooring system, X_ref [6], K_hs [6,6],
+        F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref."""
+        from .mooring_device import DeviceMooring, warm_state
+        if self.nFOWT != 1 or self.ms is not None:
+            raise NotImplementedError("solveStaticsBatch: a single FOWT with its own mooring system (arrays and "
+                                      "array-level mooring are solved by solveStatics)")
+        fowt = self.fowtList[0]
+        if fowt.ms is None:
+            raise NotImplementedError("solveStaticsBatch: the FOWT has no mooring system")
+        n = len(cases)
+        if self.mooring_currentMod > 0 and any(get_from_dict(c, "current_speed", shape=0, default=0.0) > 0
+                                               for c in cases):
+            raise NotImplementedError("solveStaticsBatch: current on the mooring lines (mooring currentMod 1)")
+        fowt.ms.current = np.zeros(3)                    # as solveStatics clears it for a case without one
+        if getattr(self, "_moor_dev", None) is None or self._moor_dev[0] is not fowt.ms:
+            self._moor_dev = (fowt.ms, DeviceMooring([fowt.ms], self.device))
+        dm = self._moor_dev[1]
+        X_ref = np.array([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0], dtype=float)
+        fowt.setPosition(X_ref)
+        fowt.calcStatics()
+        K_hs = fowt.C_struc + fowt.C_hydro
+        F_und = fowt.W_struc + fowt.W_hydro
+        warm0 = warm_state(fowt.ms)                      # the line solutions at the reference pose
+        F_const = np.zeros([n, 6])
+        for i, case in enumerate(cases):
+            ci = dict(case)
+            fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+            F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
+            if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
+                F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
+            F_const[i] = F_und + F_env
+            if F_extra is not None:
+                F_const[i] += np.asarray(F_extra[i], dtype=float)
+        return dm, X_ref, K_hs, F_const, warm0
+
+    def solveStaticsBatch(self, cases, F_extra=None, host=True):
+        """The mean offsets of many load cases in two device launches (rh_statics_solve, then
+        rh_moor_eval at the solved poses): solveStatics' Newton per case, every case's lines in
+        adjacent lanes (csrc/rh_moor.hip).  A single FOWT with its own mooring system; F_extra
+        [n, 6]: further constant loads per case.  The environmental loads are built on the host
+        as solveStatics builds them.  Returns X [n,6], Xi0 [n,6], F_moor [n,6], C_moor [n,6,6],
+        Tmoor_avg [n,2L], J_moor [n,2L,6], iters [n] (evaluations: len(Model.Xs2) of the host
+        path) and status [n] (0 = converged, else _native.MOOR_STATUS); numpy arrays, or device
+        tensors with host=False.  The model is left at its reference pose."""
+        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra)
+        n = len(cases)
+        sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)))
+        ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True)
+        torch = dm.torch
+        status = torch.maximum(sol["status"], ev["status"])
+        out = dict(X=sol["X"], Xi0=sol["X"] - torch.tensor(X_ref, dtype=torch.float64, device=dm.device),
+                   F_moor=ev["F"], C_moor=ev["K"], Tmoor_avg=ev["T"], J_moor=ev["J"], iters=sol["iters"], status=status)
+        return {k: v.cpu().numpy() for k, v in out.items()} if host else out
+
+    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk):
+        """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
+        analyzeCases solves it when the mooring is a system.  Offsets, C_moor and the tension
+        Jacobian of every case come from solveStaticsBatch; each case then gets its own
+        DeviceDesign (the FOWT moved to its pose exactly as solveStatics leaves it: turbine and
+        hydro constants at the reference pose, members and rotors at the offset pose, C_moor from
+        the device), and the drag fixed points run in chunks of pose_chunk views."""
+        import torch
+        if self.nFOWT != 1 or self.ms is not None:
+            raise NotImplementedError("analyzeCasesBatch(statics=True): arrays (their statics couple the FOWTs; "
+                                      "use analyzeCases)")
+        fowt = self.fowtList[0]
+        if fowt.potSecOrder > 0:
+            raise NotImplementedError("analyzeCasesBatch(statics=True): potSecOrder > 0 (the reference solves the "
+                                      "statics twice around the dynamics, raft/raft_model.py:301-318)")
+        if "C_moor" in (fowt._statics or {}):
+            raise NotImplementedError("analyzeCasesBatch(statics=True): the mooring stiffness was given as a fixture "
+                                      "(setStatics with a C_moor): there is no system to solve")
+        if int(pose_chunk) < 1:
+            raise ValueError("pose_chunk must be >= 1")
+        seas = [self._case_sea_states(c) for c in cases]
+        if any(len(s[0]) > 1 for s in seas):
+            raise NotImplementedError("analyzeCasesBatch(statics=True): several sea states per case")
+        self._calc_bem_once()
+        sb = self.solveStaticsBatch(cases, host=False)
+        X = sb["X"].cpu().numpy()
+        C = sb["C_moor"].cpu().numpy()
+        Fm = sb["F_moor"].cpu().numpy()
+        X_ref = np.array([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0], dtype=float)
+        n = len(cases)
+        parts = []
+        for c0 in range(0, n, int(pose_chunk)):
+            ids = range(c0, min(n, c0 + int(pose_chunk)))
+            views = []
+            for i in ids:
+                fowt.setPosition(X_ref)
+                fowt.calcTurbineConstants(dict(cases[i]), ptfm_pitch=0)
+                fowt.calcHydroConstants()
+                fowt.setPosition(X[i])
+                fowt.C_moor, fowt.F_moor0 = C[i].copy(), Fm[i].copy()
+                fowt._dd = fowt._host = None
+                dd = fowt.device_design()
+                dd.ensure_headings(np.asarray(seas[i][0], dtype=float) * DEG2RAD)
+                views.append(dd)
+            hd, sp, Hs, Tp, gm = ([seas[i][k][0] for i in ids] for k in range(5))
+            cs = CaseSet(np.arange(len(views), dtype=np.int32), hd, sp, Hs, Tp, gm)
+            res = solve_batch(views, cs, self.nIter, self.XiStart, tol, want=tuple(want))
+            parts.append({k: v.clone() for k, v in res.items()})
+            torch.cuda.synchronize(views[0].device)      # the chunk's tables are released below
+            del res, views
+        fowt.setPosition(X_ref)
+        fowt._dd = fowt._host = None
+        res = BatchResult({k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]} if parts else {})
+        if n:
+            # tension channels (mooring_outputs): amplitudes J_moor Xi, PSD over w[0] as the reference has it
+            Xi = res["Xi"]
+            J = sb["J_moor"]
+            a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2   # [n, 2L, nw]
+            res["Tmoor_PSD"] = 0.5 * a2 / float(self.w[0])
+            res["Tmoor_std"] = torch.sqrt(0.5 * a2.sum(dim=2))
+            res["Tmoor_avg"] = sb["Tmoor_avg"]
+            res["mean_offsets"] = sb["X"]
+            res["statics_iters"] = sb["iters"]
+            res["statics_status"] = sb["status"]
+        return res.host() if host else res
+
     def solveEigen(self, display=0):
         """Natural frequencies [Hz] and mode shapes of the moored system
         (raft/raft_model.py:391-476): M = M_struc + A_hydro_morison, C = C_struc + C_hydro +
@@ -486,7 +609,8 @@ class Model:
                     self.ms, self._xi_dev_all, self.w, self.device, nWaves + 1)
         return self.results
 
-    def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True):
+    def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
+                          pose_chunk=32):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -503,7 +627,16 @@ class Model:
         (f2nd_mean [n,6] of sea state 0, f2nd_mean_waves [n,nW,6] with several sea states);
         potSecOrder=1 solves twice, the QTF of each converged case's RAO between the passes
         (iters_pair [n,2]); several sea states per case raise the reference's IndexError (Q8).
-        Arrays (nFOWT > 1) go through analyzeArrayBatch: Xi [n,6N,nw], iters [n,N], ..."""
+        Arrays (nFOWT > 1) go through analyzeArrayBatch: Xi [n,6N,nw], iters [n,N], ...
+        statics=True solves every case at its own mean-offset pose with that pose's mooring stiffness,
+        as analyzeCases does when the mooring is a system: the offsets of all cases from
+        solveStaticsBatch (two device launches), then the drag fixed points in chunks of pose_chunk
+        per-case designs.  Added keys: mean_offsets [n,6], Tmoor_avg [n,2L], Tmoor_std [n,2L],
+        Tmoor_PSD [n,2L,nw] (mooring_outputs' channels), statics_iters, statics_status.  One sea state
+        per case; arrays, potSecOrder > 0 and a C_moor fixture raise NotImplementedError.
+        statics=False (the default) holds the platform at its reference position."""
+        if statics:
+            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk)
         if self.nFOWT != 1:
             return self.analyzeArrayBatch(cases, tol=tol, host=host)
         fowt = self.fowtList[0]
