@@ -173,7 +173,9 @@ int rh_version(void);
  * else the general kernel), 1 = always the general kernel, 6 = automatic, with the fast path
  * treating every node as one that needs its axial wave-table row (what a design with
  * Cd_q != 0 on every member runs; by default it streams that row only for nodes with axial side
- * drag or end drag, the others' axial terms being exact zeros: same bits either way).  Used by
+ * drag or end drag, the others' axial terms being exact zeros: same bits either way),
+ * 8 = automatic, with the two-bin fast path (512 < nw <= 1024) sweeping the nodes once per bin
+ * for the excitation (by default one sweep forms both bins': same bits either way), 9 = 6 and 8.  Used by
  * the parity tests to cross-check the device paths on the same inputs.  (Builds with -DRH_VARIANTS, made by
  * tools/build_variants.sh for on-box A/B timing only, also accept 2..5: the lock-step grouped
  * kernel, the lane-pair kernel and the two-pass launch, all measured slower) */

@@ -59,7 +59,8 @@ struct rh_ctx {
   int cur = 0;                          // slot of the last staging
   // tuning / cross-check knobs (per context: the ABI has no mutable process globals)
   bool force_general = false;   // rh_set_solver(ctx, 1): always use k_solve_cases (parity cross-checks)
-  bool all_axial = false;       // rh_set_solver(ctx, 6): k_solve_lds streams every node's axial row (cross-checks)
+  bool all_axial = false;       // rh_set_solver(ctx, 6 / 9): k_solve_lds streams every node's axial row (cross-checks)
+  bool split_c = false;         // rh_set_solver(ctx, 8 / 9): one phase-C sweep per bin (k_solve_lds_split; cross-checks)
 #ifdef RH_VARIANTS
   bool a0 = false;              // rh_set_a0: iteration-0 phase A of the fast path as a batch GEMM (rh_a0.hip;
                                 // measured slower than the per-case phase A)
@@ -221,20 +222,23 @@ int rh_version(void) { return 7; }
 int rh_set_solver(rh_ctx* ctx, int which) {
   if (!ctx) return fail(RH_EINVAL, "rh_set_solver: null context");
 #ifdef RH_VARIANTS
-  if (which < 0 || which > 6)
+  if (which < 0 || which > 9 || which == 7)
     return fail(RH_EINVAL,
                 "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 2 = ungrouped, 3 = k_solve_pair, "
-                "4 / 5 = ungrouped, k_solve_lds in one / two passes, 6 = auto with every axial row)", which);
-  ctx->no_group = which >= 2 && which != 6;
+                "4 / 5 = ungrouped, k_solve_lds in one / two passes, 6 = auto with every axial row, "
+                "8 = auto with one phase-C sweep per bin, 9 = 6 and 8)", which);
+  ctx->no_group = which >= 2 && which < 6;
   ctx->use_pair = which == 3 || (which == 0 && RH_PAIR_ON);
   ctx->two_pass = which == 5 || (which != 4 && RH_TWO_PASS);
 #else
-  if (which != 0 && which != 1 && which != 6)
-    return fail(RH_EINVAL, "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 6 = auto with every axial row; "
+  if (which != 0 && which != 1 && which != 6 && which != 8 && which != 9)
+    return fail(RH_EINVAL, "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 6 = auto with every axial row, "
+                "8 = auto with one phase-C sweep per bin, 9 = 6 and 8; "
                 "the grouped, lane-pair and two-pass kernels are tools/ubench variant builds)", which);
 #endif
   ctx->force_general = which == 1;
-  ctx->all_axial = which == 6;
+  ctx->all_axial = which == 6 || which == 9;
+  ctx->split_c = which == 8 || which == 9;
   return RH_OK;
 }
 
@@ -548,7 +552,10 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
     if (lsm <= 160 * 1024) {
       if (int r = prep_a0()) return r;
       dim3 grid(cases->ncase), block(lt);
-      const int kern = lt < rh::kLT ? rh::kSolve1x256 : nb == 1 ? rh::kSolve1x512 : rh::kSolve2x512;
+      // (two bins: both in one phase-C sweep, which parks bin 1's excitation in the case's Xi, Xi_last
+      // or F_wave block; one sweep per bin on request, or for a call that has none of the three)
+      const bool split_c = ctx->split_c || !(out->Xi || out->Xi_last || out->F_wave);
+      const int kern = lt < rh::kLT ? rh::kSolve1x256 : nb == 1 ? rh::kSolve1x512 : split_c ? rh::kSolve2x512Split : rh::kSolve2x512;
 #ifdef RH_VARIANTS
       // Two passes when the batch needs more than one round of workgroups (measured slower on
       // C2: 0.895 vs 0.828 ms).  Pass 1 runs every case up to its last possible

@@ -68,6 +68,17 @@ constexpr int kRingC = RH_RING_C; // ... of phase C (one bin per pass: less work
 #define RH_A_PAIR 1                   // 1: phase-A sums of two nodes per butterfly (tbfly4)
 #endif
 constexpr int kAxC = 4;               // axial wave-table rows phase C holds at a time (its own path, beside the ring)
+#ifndef RH_JOINT_C
+#define RH_JOINT_C 1                  // 1: k_solve_lds<2, 512> forms both bins' excitation in one phase-C node sweep
+#endif
+constexpr bool kJointC = RH_JOINT_C != 0;
+#ifndef RH_JOINT_PARK
+#define RH_JOINT_PARK 1               // 1: bin 1's excitation waits in global memory for bin 0's solve; 0: in registers (A/B)
+#endif
+// The joint sweep's ring: the kRingC slots hold one (node, bin) each, so it is kRingC / 2 nodes deep
+// with the same rows in flight (and the same registers) as the one-bin ring.
+constexpr int kRingCJ = kRingC / 2;
+static_assert(kRingC % 2 == 0, "the joint phase-C ring pairs its slots");
 // Ghost nodes: the node loops of phases A and C run whole ring rounds, so no slot of a round is
 // under a tail guard (a guarded slot is a merge point at which hipcc stops counting the ring's loads
 // and waits for all of them).  Nodes nn .. of the last round load the last node's rows
@@ -300,8 +311,15 @@ __host__ __device__ inline size_t solve_lds_smem(int nn, int nm, int NB, int LT 
 // XiLast into registers before its node loop (no global load between the ring's wave-table
 // loads) and adds each pass's node sums to the LDS partials in pass order; phase C reads and
 // writes it around each bin's solve.
+//
+// JC (joint phase C; kJointC above): one sweep of the phase-C node loop forms the excitation of both
+// bins of a thread, in the 512-thread, two-bin, one-pass kernel.  rh_solve_split.hip compiles this
+// file once more with RH_JOINT_C = 0 and the kernel renamed k_solve_lds_split: the same fixed point
+// with one sweep per bin (rh_set_solver(ctx, 8), and calls that leave no block to park bin 1's
+// excitation in).
 template <int NB, int LT = kLT, bool SER = false, int NP = 1>
 __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(CaseArgs a) {
+  constexpr bool JC = kJointC && NB == 2 && LT == kLT && !SER && NP == 1;
   constexpr int LW = LT / 64;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -607,6 +625,156 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       for (int c = 0; c < 6; ++c) fx[c] = bld(bFx, vj, c * nw16);
 #pragma unroll
       for (int c = 0; c < 6; ++c) F[c] = add(F[c], mk(okj ? fx[c].r : 0.0, okj ? fx[c].i : 0.0));
+    }
+  };
+  // The same for both bins of this thread in one sweep (JC): F[j] of bin tid + LT j.  Per bin the
+  // operations and their order are excite's, so the bits are; what is shared is everything that does
+  // not depend on the bin: the member test, fold()'s and flush()'s factor reads, the node's `al` row,
+  // the scalar row offsets.  The ring's kRingC slots hold one (node, bin) each, in the order they are
+  // consumed (node n bin 0, node n bin 1, node n + 1 bin 0, ...): each is waited for by itself, so
+  // every wait still leaves the other kRingC - 1 slots' rows outstanding, and each is refilled with
+  // the same bin of node n + kRingCJ once it is consumed.
+  auto excite2 = [&](cd (&F)[2][6]) {
+    unsigned vj[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) vj[j] = voff(tid + LT * j);
+    // (unit inertial excitation of the two bins: requested behind the node loop, in flight during
+    // the axial loop -- 48 VGPRs that the node loop, with both bins' sums and F, has no room for)
+    cd fe[2][6];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) F[j][c] = mk(0, 0);
+    {
+      cd SQ[2], S1[2], S2[2], T1[2], T2[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) SQ[j] = S1[j] = S2[j] = T1[j] = T2[j] = mk(0, 0);
+      auto load1 = [&](cd (&K)[2], int n, int j) {
+        const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) K[p] = bld(bK, vj[j], so + (unsigned)(p + 1) * nw16);
+      };
+      auto load_axial = [&](cd (&Kq)[2], int k) {   // row 0 of the k-th axial node (none past the list)
+        const int n = ax_node(k);
+        if (n >= 0) {   // uniform
+#pragma unroll
+          for (int j = 0; j < 2; ++j) Kq[j] = bld(bK, vj[j], (unsigned)n * 3u * nw16);
+        } else {
+          Kq[0] = Kq[1] = mk(0.0, 0.0);
+        }
+      };
+      int m = 0, mnext = nn > 0 ? mstart[1] : 0;
+      auto fold = [&]() {   // close member m: F += sum of its nodes, the factors read once for both bins
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          const double c1 = mbf[18 * m + RH_MF_C10 + i], c2 = mbf[18 * m + RH_MF_C20 + i];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) F[j][i] = add(F[j][i], add(scl(S1[j], c1), scl(S2[j], c2)));
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const double p1 = mbf[18 * m + RH_MF_C10 + i], p2 = mbf[18 * m + RH_MF_C20 + i];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) F[j][3 + i] = add(F[j][3 + i], sub(scl(T1[j], p2), scl(T2[j], p1)));
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) S1[j] = S2[j] = T1[j] = T2[j] = mk(0, 0);
+      };
+      // (the axial rows first, then the ring in slot order, each slot scheduled by itself: as excite)
+      cd KQ[kAxC][2];
+#pragma unroll
+      for (int r = 0; r < kAxC; ++r) load_axial(KQ[r], nn > 0 ? r : nn);
+      __builtin_amdgcn_sched_barrier(0);
+      cd K[kRingCJ][2][2];   // [node slot][bin][row]
+#pragma unroll
+      for (int r = 0; r < kRingCJ; ++r) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          load1(K[r][j], r, j);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      double A1 = al[1], A2 = al[2], A3 = al[3], A4 = al[4];
+      auto step = [&](cd (&K)[2][2], int n) {
+        while (n == mnext) {   // uniform: member m ended before node n
+          fold();
+          ++m;
+          mnext = mstart[m + 1];
+        }
+        const double a1 = A1, a2 = A2, a3 = A3, a4 = A4;
+        {
+          const double* A = al + 6 * (n + 1 < nn ? n + 1 : nn);
+          A1 = A[1]; A2 = A[2]; A3 = A[3]; A4 = A[4];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          S1[j] = add(S1[j], scl(K[j][0], a1));
+          S2[j] = add(S2[j], scl(K[j][1], a2));
+          T1[j] = add(T1[j], scl(K[j][0], a3));
+          T2[j] = add(T2[j], scl(K[j][1], a4));
+          __builtin_amdgcn_sched_barrier(0);   // consumed before the refill is issued
+          load1(K[j], n + kRingCJ, j);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+#pragma unroll 1
+      for (int n = 0; n < nn; n += kRingCJ) {   // whole rounds: the last one ends in ghost nodes
+#pragma unroll
+        for (int r = 0; r < kRingCJ; ++r) step(K[r], n + r);
+      }
+      if (nn > 0) fold();
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) fe[j][c] = bld(bFe, vj[j], c * nw16);
+      {
+        int ma = 0, mq = -1;   // the member of the node, and of the terms SQ holds
+        auto flush = [&]() {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            const double cq = mbf[18 * mq + RH_MF_CQ0 + i];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) F[j][i] = add(F[j][i], scl(SQ[j], cq));
+          }
+          SQ[0] = SQ[1] = mk(0, 0);
+        };
+        for (int k0 = 0; k0 < nn; k0 += kAxC) {
+          if (ax_node(k0) < 0) break;   // uniform: the end of the list
+#pragma unroll
+          for (int r = 0; r < kAxC; ++r) {
+            const int n = ax_node(k0 + r);
+            if (n >= 0) {   // uniform
+              while (n >= __builtin_amdgcn_readfirstlane(mstart[ma + 1])) ++ma;
+              if (ma != mq) {
+                if (mq >= 0) flush();
+                mq = ma;
+              }
+              const double aq = al[6 * n];
+#pragma unroll
+              for (int j = 0; j < 2; ++j) SQ[j] = add(SQ[j], scl(KQ[r][j], aq));
+              load_axial(KQ[r], k0 + r + kAxC);
+            }
+          }
+        }
+        if (mq >= 0) flush();
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const double z = lz[tid + LT * j];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) F[j][c] = add(scl(fe[j][c], z), scl(F[j][c], z));   // F_lin + F_drag
+    }
+    if (has_fx) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const bool okj = tid + LT * j < nw;
+        cd fx[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) fx[c] = bld(bFx, vj[j], c * nw16);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) F[j][c] = add(F[j][c], mk(okj ? fx[c].r : 0.0, okj ? fx[c].i : 0.0));
+      }
     }
   };
 
@@ -991,6 +1159,11 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         sflag[3 + ((it + 1) & 1)] = 0;
       }
     }
+#if !RH_JOINT_PARK
+    cd FR[6];   // (A/B: bin 1's excitation kept in registers across bin 0's solve)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) FR[c] = mk(0.0, 0.0);
+#endif
 #pragma unroll 1
     for (int j = 0; j < NBT; ++j) {
       // per-bin scalars picked without dynamic register indexing (the loop is not unrolled,
@@ -999,7 +1172,49 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       const bool okj = bj < nw;
       PROF_T(tc0);
       cd F[6];
-      excite(bj, F);
+      if constexpr (JC) {
+        // One sweep at bin 0 forms both bins' F.  Bin 1's is not kept in registers across bin 0's
+        // LU (24 VGPRs beside Z and F: the round-2 joint sweep spilled 113 for it): its six entries
+        // are parked in global memory, in rows only this thread touches, and read back here, where
+        // the loads' latency runs under the Z build from LDS; no streaming loop is near either end.
+        // The block is the case's Xi rows of bin 1, else its Xi_last rows (the one-pass kernels
+        // leave them unused), else its F_wave rows (the host launches k_solve_lds_split when a call
+        // has none of the three).  What a caller reads does not change: every iteration that may be
+        // the final one stores bin 1's Xi (and F_wave) below, after this read-back, so the final
+        // iteration overwrites the parked values with what the one-sweep-per-bin kernel stores; an
+        // iteration that cannot be final is followed by one that does; and a case that fails (NaN,
+        // singular) has its outputs overwritten with NaN in the epilogue.
+        rh_c128* PK = (Xo ? Xo : a.o.Xi_last ? a.o.Xi_last + c6 : a.o.F_wave + c6) + bj;
+        if (j == 0) {   // uniform
+          cd F2[2][6];
+          excite2(F2);
+#pragma unroll
+          for (int c = 0; c < 6; ++c) F[c] = F2[0][c];
+#if RH_JOINT_PARK
+          if (bj + LT < nw) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) st(PK + LT + c * nw, F2[1][c]);
+          }
+#else
+#pragma unroll
+          for (int c = 0; c < 6; ++c) FR[c] = F2[1][c];
+#endif
+        } else {
+#if RH_JOINT_PARK
+#pragma unroll
+          for (int c = 0; c < 6; ++c) F[c] = mk(0.0, 0.0);   // pad lanes: zeta = 0 gave F = 0
+          if (okj) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) F[c] = ld(PK + c * nw);
+          }
+#else
+#pragma unroll
+          for (int c = 0; c < 6; ++c) F[c] = FR[c];
+#endif
+        }
+      } else {
+        excite(bj, F);
+      }
       // F_wave: the excitation of the final iteration, which every iteration's overwrites (F is
       // live for the LU anyway), skipped once the iteration is known not to be final (below)
       if (a.o.F_wave && may_be_final()) {

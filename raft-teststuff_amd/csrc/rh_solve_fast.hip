@@ -21,6 +21,7 @@ hipError_t launch_solve_fast(int which, dim3 grid, dim3 block, size_t lsm, hipSt
     case kSolve1x256: hipLaunchKernelGGL((k_solve_lds<1, kLT / 2>), grid, block, lsm, s, a); break;
     case kSolve1x512: hipLaunchKernelGGL((k_solve_lds<1>), grid, block, lsm, s, a); break;
     case kSolve2x512: hipLaunchKernelGGL((k_solve_lds<2>), grid, block, lsm, s, a); break;
+    case kSolve2x512Split: return launch_solve_split(grid, block, lsm, s, a);
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -31,6 +32,7 @@ hipError_t occupancy_solve_fast(int which, int* per_cu, int threads, size_t lsm)
     case kSolve1x256: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<1, kLT / 2>, threads, lsm);
     case kSolve1x512: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<1>, threads, lsm);
     case kSolve2x512: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<2>, threads, lsm);
+    case kSolve2x512Split: return occupancy_solve_split(per_cu, threads, lsm);
     default: return hipErrorInvalidValue;
   }
 }

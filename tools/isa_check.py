@@ -1,7 +1,7 @@
 """ISA gate for librafthip's hot kernels (gfx950).
 
-Compiles the translation units of librafthip (raft-teststuff_amd/csrc/rh_abi.hip and
-rh_solve_fast.hip, each with its own flags from __graft_entry__.UNITS) to device assembly and
+Compiles the translation units of librafthip (raft-teststuff_amd/csrc/rh_abi.hip,
+rh_solve_fast.hip and rh_solve_split.hip, each with its own flags from __graft_entry__.UNITS) to device assembly and
 checks every kernel:
   * no dynamic register indexing: `s_set_gpr_idx_*` or `v_movrel*` (a lane-dependent index into
     a register array, lowered with a scalar index, faulted k_qtf_hankel on the box in round 2;
@@ -15,7 +15,9 @@ checks every kernel:
   * the depth the prefetch rings really keep: per streaming loop, the loads issued per trip and
     min_outstanding, the smallest vmcnt(N) waited for with loads of the loop in flight (`rings=`);
     in the two benched fixed points the phase-A and phase-C node loops must keep
-    (ring depth - 1) x loads per slot outstanding (`ringA=`, `ringC=`) -> FAIL below that.
+    (ring depth - 1) x loads per slot outstanding (`ringA=`, `ringC=`) -> FAIL below that; the joint
+    phase-C loop of the C2 kernel (both bins of a thread per node step) has its own line, `ringCJ=`;
+  * the compiler's VGPR and spilled-VGPR counts of every kernel (`vgpr=`, `spill=`), reported.
 Loops are found from the branch structure: a branch to a label that precedes it closes a loop
 [label, branch]; a loop that contains no other loop is innermost; it streams if it holds a
 buffer_load / global_load.
@@ -101,6 +103,22 @@ def kernels(lines):
     return out
 
 
+def resources(lines):
+    """{mangled name: (VGPRs, spilled VGPRs)} from the code objects' metadata notes (the compiler's own
+    counts: .vgpr_count / .vgpr_spill_count of each kernel entry, which follow its .name)."""
+    out, name = {}, None
+    for ln in lines:
+        m = re.match(r"^\s*(?:- )?\.(name|vgpr_count|vgpr_spill_count):\s+(\S+)", ln)
+        if not m:
+            continue
+        if m.group(1) == "name":
+            name = m.group(2)
+        elif name is not None:
+            v, sp = out.get(name, (None, None))
+            out[name] = (int(m.group(2)), sp) if m.group(1) == "vgpr_count" else (v, int(m.group(2)))
+    return out
+
+
 VMCNT = re.compile(r"^\s*s_waitcnt\s+(?:.*\s)?vmcnt\((\d+)\)")
 SCRATCH_LOAD = re.compile(r"^\s*(scratch_load|buffer_load\w*.*\boff(en)?\b.*s\[0:3\])")
 
@@ -171,6 +189,20 @@ def ring_depths():
 RING_GATED = ("k_solve_lds<2, 512, false, 1>", "k_solve_lds<2, 128, true, 1>")
 
 
+# The kernel whose phase C takes both bins of a thread in one node sweep (rh_solve.hip, kJointC): its
+# kRingC slots hold one (node, bin) each, 2 rows, so a trip of kRingC / 2 nodes issues as many loads as
+# a trip of the one-bin loop, and a wait for one slot leaves (kRingC - 1) x 2 outstanding (`ringCJ=`).
+JOINT_C = ("k_solve_lds<2, 512, false, 1>",)
+
+
+def joint_gate(rings):
+    """(loads per trip, min_outstanding, needed) of the joint phase-C node loop."""
+    _, rc = ring_depths()
+    per_trip = (rc // 2) * 4
+    hit = [m for l, m in rings if l == per_trip]
+    return per_trip, None if not hit or None in hit else min(hit), (rc - 1) * 2
+
+
 def ring_gate(rings):
     """[(name, loads, min_outstanding, needed)] of the two gated loops among a kernel's streaming loops,
     picked by their loads per trip (the short axial loops issue fewer)."""
@@ -224,7 +256,8 @@ def main():
     args = ap.parse_args()
     path = args.asm or compile_asm(["-D" + d for d in args.D])
     with open(path) as fh:
-        ks = kernels(fh.read().split("\n"))
+        lines = fh.read().split("\n")
+    ks, res = kernels(lines), resources(lines)
     rows, fails = [], []
     for name, body in sorted(ks.items()):
         r = analyse(body)
@@ -253,6 +286,14 @@ def main():
                 if (low is None or low < need) and not args.no_ring_gate and not verdict.startswith("FAIL"):
                     verdict = (f"FAIL phase-{ph} ring ({per_trip} loads per trip): min_outstanding "
                                f"{'not found' if low is None else low} < {need}")
+        if any(k in dn for k in JOINT_C):
+            per_trip, low, need = joint_gate(r["rings"])
+            rings += f" ringCJ={'?' if low is None else low}>={need}"
+            if (low is None or low < need) and not args.no_ring_gate and not verdict.startswith("FAIL"):
+                verdict = (f"FAIL joint phase-C ring ({per_trip} loads per trip): min_outstanding "
+                           f"{'not found' if low is None else low} < {need}")
+        vg, sp = res.get(name, (None, None))
+        rings += f" vgpr={'?' if vg is None else vg} spill={'?' if sp is None else sp}"
         if verdict.startswith("FAIL"):
             fails.append(dn)
         rows.append(f"{dn:70s} hot={int(hot)} loops={r['loops']:3d} inner={r['inner']:3d} "
