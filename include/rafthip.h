@@ -276,7 +276,8 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
  * The device form of raft/mooring.py for ONE coupled body whose lines each join one fixed point
  * and one body-attached point (no free points, no current on the lines, W >= 0), and of
  * Model.solveStatics' Newton on it.  One lane per (pose, line); the lines of a pose sit in
- * adjacent lanes of a group of the next power of two >= the largest nline, at most 64. */
+ * adjacent lanes of a group of the next power of two >= the largest nline, at most 64.
+ * Several bodies, free points and shared lines: rh_moor_array_eval / rh_array_statics_solve below. */
 enum rh_moor_line_field {
   RH_ML_FX, RH_ML_FY, RH_ML_FZ, /* fixed end, global [m] */
   RH_ML_AX, RH_ML_AY, RH_ML_AZ, /* attached end, body frame [m] */
@@ -320,6 +321,79 @@ int rh_moor_eval(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* s
 int rh_statics_solve(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int ncase,
                      const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
                      const double* warm0, double* X, double* warm, int* iters, int* status, rh_stream stream);
+
+/* ---- general mooring systems and the mean offsets of moored arrays (csrc/rh_moor_array.h, .hip) ----
+ * The device form of raft/mooring.py for several coupled bodies (one per FOWT), free points solved
+ * for equilibrium (MooringSystem.solve_equilibrium, dsolve2 on their coordinates), lines between a
+ * body and an anchor, two bodies, two points of one body, a free point and anything, and of
+ * Model.solveStatics' Newton for N FOWTs.  One record merges every system a model's statics see
+ * (each FOWT's own system and the array-level system): a point table, a line table that carries
+ * each line's own depth and catenary tolerance, and the system each line came from.
+ * Not covered (refused in raft/mooring_array_device.py): current on the lines, buoyant lines
+ * (W < 0), a line joining two fixed points, free points in more than one of the merged systems.
+ * One lane per (pose, line), the lines of a pose in one group of a wave, one wave per workgroup;
+ * the dense work of a pose on its LDS workspace (csrc/rh_moor_array.hip). */
+enum rh_moor_point_field {
+  RH_MP_KIND,                /* 0 fixed, 1 attached to a body, 2 free */
+  RH_MP_INDEX,               /* body index (kind 1) or free-point index (kind 2), else 0 */
+  RH_MP_X, RH_MP_Y, RH_MP_Z, /* global (fixed), body frame (attached), start position (free) [m] */
+  RH_MP_M,                   /* mass [kg] */
+  RH_MP_V,                   /* volume [m^3] */
+  RH_MP_COUNT
+};
+enum rh_moor_aline_field {
+  RH_MAL_A, RH_MAL_B, /* point index of end A and of end B */
+  RH_MAL_L,           /* unstretched length [m] */
+  RH_MAL_EA,          /* axial stiffness [N] */
+  RH_MAL_W,           /* wet weight per length [N/m], >= 0 */
+  RH_MAL_DEPTH,       /* depth of the system the line came from [m] */
+  RH_MAL_TOL,         /* cat_tol of that system */
+  RH_MAL_SYS,         /* membership: which of the merged systems the line came from */
+  RH_MAL_COUNT
+};
+#define RH_MOOR_MAX_BODIES 4
+#define RH_MOOR_MAX_FREE 8
+/* (at most RH_MOOR_MAX_LINES lines in total) */
+
+typedef struct {
+  int nbody, npoint, nline, nfree;
+  int free_sys, pad_;          /* the RH_MAL_SYS value of the system that holds the free points, or -1 */
+  double g, rho;               /* of that system: weight and buoyancy of the free points */
+  double free_tol;             /* MooringSystem.free_tol: the free-point step tolerance [m] */
+  double free_depth;           /* that system's depth: a free-point step is capped at depth / 10 (10 m if <= 0) */
+  const double* point;         /* device [RH_MP_COUNT][npoint], struct of arrays */
+  const double* line;          /* device [RH_MAL_COUNT][nline] */
+  const double* point_host;    /* the same two tables in host memory: validated before the launch */
+  const double* line_host;
+} rh_moor_array_system;
+
+/* status values of the two calls below: those of rh_moor_eval / rh_statics_solve (6 = singular
+ * 6nb x 6nb step matrix), and 8 free-point equilibrium not converged within 500 evaluations,
+ * 9 singular free-point / condensation matrix. */
+
+/* Equilibrium of the free points, forces, analytic (condensed) stiffness and end tensions,
+ * optionally the tension Jacobian, of npose poses.  sys / sys_dev / sys_idx as rh_moor_eval.  With
+ * nb, nl, nf the largest nbody, nline, nfree of sys[0..nsys): r6 [npose][nb][6]; warm
+ * [npose][nl][2] and free [npose][nf][3] (may be NULL when nf = 0) are read as the start (warm 0 =
+ * cold) and overwritten with the solution.  F [npose][6nb] = coupled_forces(lines_only=True); K
+ * [npose][6nb][6nb] = coupled_stiffness_analytic(); T [npose][2nl]: TA of line l in column l, TB
+ * in column nl + l; J [npose][2nl][6nb] or NULL: dT/dX by central differences (0.1 m, 0.1 rad) over
+ * all 6nb DOFs, every perturbed equilibrium started from the pose's own line state and free
+ * points.  nev [npose] or NULL: line passes of the pose's own equilibrium (1 + dsolve2 evaluations
+ * + 1; 1 without free points).  Entries a record lacks are zeros.  status: device [npose]. */
+int rh_moor_array_eval(rh_ctx* ctx, const rh_moor_array_system* sys, const rh_moor_array_system* sys_dev, int nsys,
+                       int npose, const int* sys_idx, const double* r6, double* warm, double* free_pts, double* F,
+                       double* K, double* T, double* J, int* nev, int* status, rh_stream stream);
+
+/* Mean offsets of ncase cases: Model.solveStatics (statics_mod 0, forcing_mod 0) of N FOWTs on the
+ * record, dsolve2(a_max = 1.6, maxIter = 20).  X_ref [ncase][nb][6]; K_hs [ncase][nb][36] = C_struc +
+ * C_hydro of each FOWT; F_const [ncase][nb][6] = W_struc + W_hydro + F_env; warm0 [ncase][nl][2] or
+ * NULL (cold) and free0 [ncase][nf][3]: the state at X_ref.  Out: X [ncase][6nb] (the last evaluated
+ * pose), warm, free (the state at X), iters [ncase] (outer evaluations, len(Model.Xs2)), status. */
+int rh_array_statics_solve(rh_ctx* ctx, const rh_moor_array_system* sys, const rh_moor_array_system* sys_dev, int nsys,
+                           int ncase, const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
+                           const double* warm0, const double* free0, double* X, double* warm, double* free_pts,
+                           int* iters, int* status, rh_stream stream);
 
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
@@ -455,6 +529,13 @@ int rh_array_response_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, 
 int rh_array_solve_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase, const int* design_idx,
                          const double* B_drag, const double* K, rh_c128* Xi, double dw, double* psd, double* std_,
                          rh_stream stream);
+
+/* rh_array_solve_stats with a stiffness per case: case ic reads K + ic * K_stride doubles (K_stride
+ * >= 36 nf^2; each case at its own mean-offset pose has its own array stiffness).  K_stride = 0: one
+ * K for every case, which is rh_array_solve_stats. */
+int rh_array_solve_stats_ext(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase,
+                             const int* design_idx, const double* B_drag, const double* K, long long K_stride,
+                             rh_c128* Xi, double dw, double* psd, double* std_, rh_stream stream);
 
 /* ------------------------------------------------------------------------------------
  * Slender-body second-order QTF (FOWT.calcQTF_slenderBody, raft/raft_fowt.py:1385-1648)

@@ -447,6 +447,7 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
 
 }  // extern "C" (rh_moor.h has templates; the two calls take their linkage from rafthip.h)
 #include "rh_moor.hip"   // k_moor_eval, k_statics_solve + rh_moor_eval, rh_statics_solve (uses fail / RH_HIP above)
+#include "rh_moor_array.hip"   // k_moor_array_eval, k_array_statics_solve + their two ABI calls
 extern "C" {
 
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,
@@ -838,24 +839,26 @@ int rh_array_response_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, 
 
 // The response step alone, with F already in Xi (rh_solve_out.F_wave of the fixed point): the
 // block solve and the statistics of k_array_resp, no excitation launch.
-int rh_array_solve_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase, const int* design_idx,
-                         const double* B_drag, const double* K, rh_c128* Xi, double dw, double* psd, double* std_,
-                         rh_stream stream) {
-  if (!ctx || !designs || !design_idx || !B_drag || !Xi) return fail(RH_EINVAL, "rh_array_solve_stats: null argument");
-  if ((psd || std_) && !(dw > 0)) return fail(RH_EINVAL, "rh_array_solve_stats: dw=%g", dw);
-  if (nf < 1 || nf > 2) return fail(RH_EINVAL, "rh_array_solve_stats: nf=%d (supported: 1, 2)", nf);
-  if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "rh_array_solve_stats: ncase=%d", ncase);
-  if (ndesign < 1) return fail(RH_EINVAL, "rh_array_solve_stats: ndesign=%d", ndesign);
+static int array_solve_stats(const char* who, rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase,
+                             const int* design_idx, const double* B_drag, const double* K, long long K_stride, rh_c128* Xi,
+                             double dw, double* psd, double* std_, rh_stream stream) {
+  if (!ctx || !designs || !design_idx || !B_drag || !Xi) return fail(RH_EINVAL, "%s: null argument", who);
+  if ((psd || std_) && !(dw > 0)) return fail(RH_EINVAL, "%s: dw=%g", who, dw);
+  if (nf < 1 || nf > 2) return fail(RH_EINVAL, "%s: nf=%d (supported: 1, 2)", who, nf);
+  if (K_stride != 0 && (!K || K_stride < 36LL * nf * nf))
+    return fail(RH_EINVAL, "%s: K_stride=%lld (0, or >= %d with a K)", who, K_stride, 36 * nf * nf);
+  if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "%s: ncase=%d", who, ncase);
+  if (ndesign < 1) return fail(RH_EINVAL, "%s: ndesign=%d", who, ndesign);
   const int nw = designs[0].nw;
   for (int i = 0; i < ndesign; ++i) {
     if (int r = check_design(designs[i], false)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "rh_array_solve_stats: all designs must share nw");
+    if (designs[i].nw != nw) return fail(RH_EINVAL, "%s: all designs must share nw", who);
   }
   RH_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   if (int r = stage_designs(ctx, designs, ndesign, s)) return r;
   rh::ArrayArgs a{staged_designs(ctx), ncase, design_idx, nullptr, nullptr, B_drag, nullptr, K, Xi, 0, 0, dw, psd, std_,
-                  nullptr};
+                  nullptr, K_stride};
   const dim3 g(ncase), gr(rh::kArrRespThreads);
   const bool multi = nw > rh::kArrRespThreads;
   if (nf == 1) {
@@ -867,6 +870,21 @@ int rh_array_solve_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, int
   }
   RH_HIP(hipGetLastError());
   return designs_used(ctx, s);
+}
+
+int rh_array_solve_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase, const int* design_idx,
+                         const double* B_drag, const double* K, rh_c128* Xi, double dw, double* psd, double* std_,
+                         rh_stream stream) {
+  return array_solve_stats("rh_array_solve_stats", ctx, designs, ndesign, nf, ncase, design_idx, B_drag, K, 0, Xi, dw, psd,
+                           std_, stream);
+}
+
+// ... with case ic reading its own stiffness at K + ic K_stride (0 = one K for every case)
+int rh_array_solve_stats_ext(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase,
+                             const int* design_idx, const double* B_drag, const double* K, long long K_stride,
+                             rh_c128* Xi, double dw, double* psd, double* std_, rh_stream stream) {
+  return array_solve_stats("rh_array_solve_stats_ext", ctx, designs, ndesign, nf, ncase, design_idx, B_drag, K, K_stride,
+                           Xi, dw, psd, std_, stream);
 }
 
 long long rh_qtf_workspace_bytes(const rh_qtf_design* q) {

@@ -1076,13 +1076,14 @@ struct ArrayArgs {
   const double* zeta;          // [ncase * NF][nw]
   const double* B_drag;        // [ncase * NF][36]
   const double* Bmat;          // [ncase * NF][nn_max][9] (FOWTs may differ in node count)
-  const double* K;             // [6 NF][6 NF] array stiffness, or NULL
+  const double* K;             // [6 NF][6 NF] array stiffness (case ic reads K + ic K_stride), or NULL
   rh_c128* Xi;                 // [ncase][6 NF][nw]: F from k_array_exc, then the response
   int nn_max, nm_max;          // largest node / member counts of the designs (dynamic LDS layout)
   double dw = 0;               // motion statistics (k_array_resp): frequency step,
   double* psd = nullptr;       // [ncase * NF][6][nw] or NULL,
   double* stdv = nullptr;      // [ncase * NF][6] or NULL
   const int* order = nullptr;  // k_array_exc: entries in launch order (design, then heading), or NULL
+  long long K_stride = 0;      // k_array_resp: doubles between the K of successive cases (0 = one K shared)
 };
 constexpr int kArrRespThreads = 256;   // k_array_resp: one case per workgroup, bins in chunks of 256
 constexpr int kArrExcThreads = 256;
@@ -1207,7 +1208,7 @@ __global__ __launch_bounds__(kArrRespThreads) void k_array_resp(ArrayArgs a) {
   __shared__ double sred[W][N];       // motion RMS: the waves' sums
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int ic = blockIdx.x;
-  for (int e = tid; e < N * N; e += kArrRespThreads) ks[e] = a.K ? a.K[e] : 0.0;
+  for (int e = tid; e < N * N; e += kArrRespThreads) ks[e] = a.K ? a.K[(size_t)ic * (size_t)a.K_stride + e] : 0.0;
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
     const rh_design& d = a.designs[a.design_idx[ic * NF + f]].d;

@@ -76,7 +76,26 @@ ML_COUNT = len(MOOR_LINE_FIELDS)
 MOOR_MAX_LINES = 64
 MOOR_STATUS = {0: "ok", 1: "catenary: XF < 0", 2: "catenary: L <= 0", 3: "catenary: EA <= 0",
                4: "catenary did not converge", 5: "statics Newton did not converge", 6: "singular step matrix",
-               7: "system index out of range"}
+               7: "system index out of range",
+               8: "free-point equilibrium not converged within 500 evaluations",
+               9: "singular free-point / condensation matrix"}
+
+
+class RhMoorArraySystem(ctypes.Structure):
+    _fields_ = [("nbody", ctypes.c_int), ("npoint", ctypes.c_int), ("nline", ctypes.c_int), ("nfree", ctypes.c_int),
+                ("free_sys", ctypes.c_int), ("pad_", ctypes.c_int), ("g", ctypes.c_double), ("rho", ctypes.c_double),
+                ("free_tol", ctypes.c_double), ("free_depth", ctypes.c_double), ("point", _p), ("line", _p),
+                ("point_host", _p), ("line_host", _p)]
+
+
+# point-table and line-table row order of a general system (enum rh_moor_point_field, rh_moor_aline_field)
+MOOR_POINT_FIELDS = ["KIND", "INDEX", "X", "Y", "Z", "M", "V"]
+MP = {name: i for i, name in enumerate(MOOR_POINT_FIELDS)}
+MP_COUNT = len(MOOR_POINT_FIELDS)
+MOOR_ALINE_FIELDS = ["A", "B", "L", "EA", "W", "DEPTH", "TOL", "SYS"]
+MAL = {name: i for i, name in enumerate(MOOR_ALINE_FIELDS)}
+MAL_COUNT = len(MOOR_ALINE_FIELDS)
+ARR_MAX_BODIES, ARR_MAX_FREE = 4, 8
 
 
 class NativeError(RuntimeError):
@@ -114,6 +133,10 @@ def lib():
                                  _p, _p, _p],
                 "rh_statics_solve": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,
                                      _p, _p, _p, _p, _p, _p],
+                "rh_moor_array_eval": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p,
+                                       _p, _p, _p, _p, _p, _p, _p, _p],
+                "rh_array_statics_solve": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p,
+                                           _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,
@@ -136,6 +159,8 @@ def lib():
                                             _p, _p, _p, _p, _p, _p, _p, ctypes.c_double, _p, _p, _p, _p],
                 "rh_array_solve_stats": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, ctypes.c_int, _p, _p,
                                          _p, _p, ctypes.c_double, _p, _p, _p],
+                "rh_array_solve_stats_ext": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, ctypes.c_int, _p,
+                                             _p, _p, ctypes.c_longlong, _p, ctypes.c_double, _p, _p, _p],
                 "rh_wave_excitation": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p,
                                        _p],
                 "rh_channel_stats": [_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _p,

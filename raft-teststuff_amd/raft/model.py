@@ -11,6 +11,9 @@ By default the batch does not solve mean offsets (solveStatics: MoorPy equilibri
 stays at its reference position, exactly the state the goldens are generated in.
   Model.solveStaticsBatch(cases)  the mean offsets of every case on the device (csrc/rh_moor.hip);
   analyzeCasesBatch(cases, statics=True) solves each case at its own offset pose, as analyzeCases does.
+  Model.solveStaticsArrayBatch(cases)  the same for moored arrays: N FOWTs on the array-level system
+  and / or their own systems, free points included (csrc/rh_moor_array.hip);
+  analyzeArrayBatch(cases, statics=True) solves each case of the farm at its own offset poses.
 """
 import ctypes
 
@@ -403,6 +406,133 @@ class Model:
         out = dict(X=sol["X"], Xi0=sol["X"] - torch.tensor(X_ref, dtype=torch.float64, device=dm.device),
                    F_moor=ev["F"], C_moor=ev["K"], Tmoor_avg=ev["T"], J_moor=ev["J"], iters=sol["iters"], status=status)
         return {k: v.cpu().numpy() for k, v in out.items()} if host else out
+
+    def _statics_array_inputs(self, cases, F_extra=None):
+        """The host side of solveStaticsArrayBatch: the merged record and one record per system,
+        X_ref [N,6], K_hs [N,6,6], F_const [n,N,6] and the state (line warm starts, free
+        points) of every system with the FOWTs at their reference poses.  Every refusal is raised
+        before the device is touched."""
+        from .mooring_array_device import array_state, flatten_array
+        own = [f.ms for f in self.fowtList]
+        if self.ms is None and all(s is None for s in own):
+            raise NotImplementedError("solveStaticsArrayBatch: the model has no mooring system")
+        if self.mooring_currentMod > 0 and any(get_from_dict(c, "current_speed", shape=0, default=0.0) > 0
+                                               for c in cases):
+            raise NotImplementedError("solveStaticsArrayBatch: current on the mooring lines (mooring currentMod 1)")
+        for c in cases:
+            if isinstance(c.get("wind_speed"), list) and len(c["wind_speed"]) != len(self.fowtList):
+                raise IndexError("List of wind speeds must be the same length as the list of wind turbines")
+        for sysm in [self.ms] + own:
+            if sysm is not None:
+                sysm.current = np.zeros(3)               # as solveStatics clears it for a case without one
+        rec = flatten_array(self)                        # (refusals: before any device call)
+        if rec.nbody != self.nFOWT:
+            raise NotImplementedError("solveStaticsArrayBatch: the last FOWT has no mooring line")
+        subs = [rec] if len(rec.systems) == 1 else [rec] + [flatten_array([(ms, range(len(ms.bodies)))])
+                                                            for ms, _ in rec.systems]
+        nf, n = self.nFOWT, len(cases)
+        X_ref = np.zeros([nf, 6])
+        K_hs, F_und = np.zeros([nf, 6, 6]), np.zeros([nf, 6])
+        for i, fowt in enumerate(self.fowtList):
+            X_ref[i, :2] = fowt.x_ref, fowt.y_ref
+            fowt.setPosition(X_ref[i])
+            fowt.calcStatics()
+            K_hs[i] = fowt.C_struc + fowt.C_hydro
+            F_und[i] = fowt.W_struc + fowt.W_hydro
+        if self.ms is not None:
+            self.ms.set_body_positions(list(X_ref))
+        warm0, free0 = array_state(rec)                  # the state at the reference poses, read once
+        F_const = np.zeros([n, nf, 6])
+        for ic, case in enumerate(cases):
+            for i, fowt in enumerate(self.fowtList):
+                ci = dict(case)
+                if isinstance(case.get("wind_speed"), list):
+                    ci["wind_speed"] = case["wind_speed"][i]
+                fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+                fowt.calcHydroConstants()
+                F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
+                if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
+                    F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
+                F_const[ic, i] = F_und[i] + F_env
+        if F_extra is not None:
+            F_const += np.asarray(F_extra, dtype=float).reshape(n, nf, 6)
+        return rec, subs, X_ref, K_hs, F_const, warm0, free0
+
+    def solveStaticsArrayBatch(self, cases, F_extra=None, host=True):
+        """The mean offsets of many load cases of N >= 1 FOWTs moored by the array-level system and / or
+        their own systems, in two device launches (rh_array_statics_solve on the merged record, then
+        rh_moor_array_eval of every system at the solved poses): Model.solveStatics' Newton per case
+        with the free points' equilibrium inside every evaluation (csrc/rh_moor_array.hip).  Every case
+        starts from the state of the model at its reference poses (line warm starts and free points
+        read once, after moving the FOWTs there and re-solving), so a case's result is solveStatics'
+        on a freshly built model.  F_extra [n, 6N]: further constant loads.  Returns X [n,6N], Xi0,
+        F_moor [n,6N], K_array [n,6N,6N] (the array system's share), C_moor / F_moor0 (per FOWT: its
+        own system's [n,6,6] / [n,6], or None), Tmoor_avg [n,2L] and J_moor [n,2L,6N] of the array
+        system (None without one), Tmoor_avg_own / J_moor_own (per FOWT, [n,2Li] / [n,2Li,6] or None),
+        iters [n] (evaluations: len(Model.Xs2) of the host path), status [n] (0 = converged, else
+        _native.MOOR_STATUS); numpy arrays, or device tensors with host=False.  The model is left at
+        its reference pose."""
+        from .mooring_array_device import DeviceArrayMooring
+        rec, subs, X_ref, K_hs, F_const, warm0, free0 = self._statics_array_inputs(cases, F_extra)
+        # the device records are kept between calls while the freshly flattened tables equal theirs
+        dm = getattr(self, "_moor_arr_dev", None)
+        if dm is None or dm.dev_index != self.device or not dm.same_tables(subs):
+            dm = self._moor_arr_dev = DeviceArrayMooring(subs, self.device)
+        torch = dm.torch
+        n, nf = len(cases), self.nFOWT
+        nb, nl, nfp = dm.nb, dm.nl, dm.nf
+        f64 = dict(dtype=torch.float64, device=dm.device)
+
+        def padded(a, rows, width):
+            out = np.zeros([rows, width])
+            out[:a.shape[0]] = a
+            return out
+        rep = lambda a: np.tile(a, (n,) + (1,) * a.ndim)   # noqa: E731
+        sol = dm.solve_statics(rep(padded(X_ref, nb, 6)), rep(np.concatenate([K_hs, np.zeros([nb - nf, 6, 6])])),
+                               np.concatenate([F_const, np.zeros([n, nb - nf, 6])], axis=1), rep(padded(warm0, nl, 2)),
+                               rep(padded(free0, nfp, 3)), sys_idx=np.zeros(n, dtype=np.int32))
+        X = sol["X"][:, :6 * nf]
+        # every system at the solved poses: its share of force and stiffness, its tensions and their Jacobian
+        ns = len(rec.systems)
+        first = 0 if ns == 1 else 1
+        r6 = torch.zeros([ns, n, nb, 6], **f64)
+        wm = torch.zeros([ns, n, nl, 2], **f64)
+        fr = torch.zeros([ns, n, nfp, 3], **f64)
+        for k, (ms, bodies) in enumerate(rec.systems):
+            for j, b in enumerate(bodies):
+                r6[k, :, j] = X[:, 6 * b:6 * b + 6]
+            rows = torch.tensor(rec.lines_of(k), dtype=torch.long, device=dm.device)
+            wm[k, :, :len(rows)] = sol["warm"][:, rows]
+            if k == rec.free_sys:
+                fr[k, :, :rec.nfree] = sol["free"][:, :rec.nfree]
+        ev = dm.eval(r6.view(ns * n, nb, 6), wm.view(ns * n, nl, 2), fr.view(ns * n, nfp, 3),
+                     sys_idx=np.repeat(np.arange(first, first + ns, dtype=np.int32), n), jacobian=True)
+        Fk, Kk = ev["F"].view(ns, n, 6 * nb), ev["K"].view(ns, n, 6 * nb, 6 * nb)
+        Tk, Jk = ev["T"].view(ns, n, 2 * nl), ev["J"].view(ns, n, 2 * nl, 6 * nb)
+        status = torch.maximum(sol["status"], ev["status"].view(ns, n).max(dim=0).values)
+        F_moor = torch.zeros([n, 6 * nf], **f64)
+        out = dict(X=X.contiguous(), K_array=torch.zeros([n, 6 * nf, 6 * nf], **f64), C_moor=[None] * nf,
+                   F_moor0=[None] * nf, Tmoor_avg=None, J_moor=None, Tmoor_avg_own=[None] * nf, J_moor_own=[None] * nf)
+        for k, (ms, bodies) in enumerate(rec.systems):
+            L = len(ms.lines)
+            cols = list(range(L)) + list(range(nl, nl + L))
+            dof = [6 * j + d for j in range(len(bodies)) for d in range(6)]
+            T, J = Tk[k][:, cols].contiguous(), Jk[k][:, cols][:, :, dof].contiguous()
+            for j, b in enumerate(bodies):
+                F_moor[:, 6 * b:6 * b + 6] += Fk[k][:, 6 * j:6 * j + 6]
+            if ms is self.ms:
+                out["K_array"] = Kk[k][:, :6 * nf, :6 * nf].contiguous()
+                out["Tmoor_avg"], out["J_moor"] = T, J
+            else:
+                i = bodies[0]
+                out["C_moor"][i], out["F_moor0"][i] = Kk[k][:, :6, :6].contiguous(), Fk[k][:, :6].contiguous()
+                out["Tmoor_avg_own"][i], out["J_moor_own"][i] = T, J
+        out.update(Xi0=out["X"] - torch.tensor(X_ref.reshape(-1), **f64), F_moor=F_moor, iters=sol["iters"], status=status,
+                   free=sol["free"])
+        if not host:
+            return out
+        cpu = lambda v: None if v is None else v.cpu().numpy()   # noqa: E731
+        return {k: [cpu(x) for x in v] if isinstance(v, list) else cpu(v) for k, v in out.items()}
 
     def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk):
         """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
@@ -800,7 +930,8 @@ class Model:
                     arr=(N.RhDesign * nf)(*[d.struct() for d in dds]),
                     K=None if Ka is None else torch.tensor(Ka, dtype=torch.float64, device=dev).contiguous())
 
-    def analyzeArrayBatch(self, cases=None, tol=0.01, host=True, marks=None, prepared=None):
+    def analyzeArrayBatch(self, cases=None, tol=0.01, host=True, marks=None, prepared=None, statics=False,
+                          pose_chunk=32):
         """The coupled-array response of many cases (raft/raft_model.py:852-1065 for nFOWT > 1)
         in a few device calls instead of per-case, per-FOWT host round trips:
           1. every (case, FOWT) drag fixed point in one rh_solve_cases launch (outputs: zeta,
@@ -819,8 +950,17 @@ class Model:
         (:903-904, :1059-1061; f2nd_mean [n, N, 6]).
         Returns Xi [n, 6N, nw], iters / status [n, N], psd [n, N, 6, nw], std [n, N, 6], zeta.
         prepared: prepareArrayBatch(cases) of an earlier call (then `cases` is not needed).
-        marks: optional two timing events recorded around the fixed-point launch (bench)."""
+        marks: optional two timing events recorded around the fixed-point launch (bench).
+        statics=True solves every case at its own mean-offset pose, as analyzeCases does: the offsets
+        of all cases from solveStaticsArrayBatch, every (case, FOWT) design at its own pose in chunks
+        of pose_chunk cases, and the coupled solve with the case's own array stiffness
+        (rh_array_solve_stats_ext).  Added keys: mean_offsets [n,6N], statics_iters, statics_status,
+        and the reference's array_mooring channels (raft/raft_model.py:351-373) Tmoor_avg [n,2L],
+        Tmoor_std, Tmoor_PSD [n,2L,nw] (over w[0]), Tmoor_max / Tmoor_min (+- 3 std).  One sea state
+        per case; potSecOrder > 0 and a K_array / C_moor fixture raise NotImplementedError."""
         import torch
+        if statics:
+            return self._analyze_array_statics(cases, tol, host, pose_chunk)
         P = prepared if prepared is not None else self.prepareArrayBatch(cases)
         nf, n, nw = self.nFOWT, P["n"], self.nw
         dds, cs, prep, dev = P["dds"], P["cs"], P["prep"], P["dev"]
@@ -858,6 +998,86 @@ class Model:
         if host:
             return {k: v.cpu().numpy() for k, v in out.items() if k != "_keep"}
         return out
+
+    def _analyze_array_statics(self, cases, tol, host, pose_chunk):
+        """analyzeArrayBatch(statics=True): see there.  Every FOWT is moved to its pose as solveStatics
+        leaves it (turbine and hydro constants at the reference pose, members and rotors at the
+        offset pose, its own system's C_moor from the device)."""
+        import torch
+        from .solver import prepare_batch
+        if any(f.potSecOrder > 0 for f in self.fowtList):
+            raise NotImplementedError("analyzeArrayBatch(statics=True): potSecOrder > 0 (the reference solves the "
+                                      "statics twice around the dynamics, raft/raft_model.py:301-318)")
+        if self.K_array is not None or any("C_moor" in (f._statics or {}) for f in self.fowtList):
+            raise NotImplementedError("analyzeArrayBatch(statics=True): the mooring stiffness was given as a fixture "
+                                      "(K_array, or setStatics with a C_moor): there is no system to solve")
+        if int(pose_chunk) < 1:
+            raise ValueError("pose_chunk must be >= 1")
+        seas = [self._case_sea_states(c) for c in cases]
+        if any(len(s[0]) > 1 for s in seas):
+            raise NotImplementedError("analyzeArrayBatch(statics=True): several sea states per case")
+        self._calc_bem_once()
+        sb = self.solveStaticsArrayBatch(cases, host=False)
+        nf, n, nw = self.nFOWT, len(cases), self.nw
+        Xs = sb["X"].cpu().numpy()
+        Cm = [None if c is None else c.cpu().numpy() for c in sb["C_moor"]]
+        Fm = [None if c is None else c.cpu().numpy() for c in sb["F_moor0"]]
+        X_ref = np.array([[f.x_ref, f.y_ref, 0, 0, 0, 0] for f in self.fowtList], dtype=float)
+        dev = sb["X"].device
+        ctx, s = N.context(self.device), N.stream_handle(torch, dev)
+        parts = []
+        for c0 in range(0, n, int(pose_chunk)):
+            ids = list(range(c0, min(n, c0 + int(pose_chunk))))
+            dds = []
+            for i in ids:
+                for f, fowt in enumerate(self.fowtList):
+                    ci = dict(cases[i])
+                    if isinstance(ci.get("wind_speed"), list):
+                        ci["wind_speed"] = ci["wind_speed"][f]
+                    fowt.setPosition(X_ref[f])
+                    fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+                    fowt.calcHydroConstants()
+                    fowt.setPosition(Xs[i, 6 * f:6 * f + 6])
+                    if Cm[f] is not None:
+                        fowt.C_moor, fowt.F_moor0 = Cm[f][i].copy(), Fm[f][i].copy()
+                    fowt._dd = fowt._host = None
+                    dd = fowt.device_design()
+                    dd.ensure_headings(np.asarray(seas[i][0], dtype=float) * DEG2RAD)
+                    dds.append(dd)
+            m = len(ids)
+            rep = lambda k: [seas[i][k][0] for i in ids for _ in range(nf)]   # noqa: E731
+            cs = CaseSet(np.arange(m * nf, dtype=np.int32), rep(0), rep(1), rep(2), rep(3), rep(4))
+            prep = prepare_batch(dds, cs)
+            X = torch.empty([m, 6 * nf, nw], dtype=torch.complex128, device=dev)
+            res = solve_batch_2nd(dds, [self.fowtList[k % nf] for k in range(m * nf)], cs, self.nIter, self.XiStart, tol,
+                                  want=("zeta", "Bmat", "B_drag", "noXi"), prepared=prep, F_wave=X.view(m * nf, 6, nw))
+            arr = (N.RhDesign * (m * nf))(*[d.struct() for d in dds])
+            K = sb["K_array"][ids[0]:ids[-1] + 1].contiguous()
+            psd = torch.empty([m * nf, 6, nw], dtype=torch.float64, device=dev)
+            std = torch.empty([m * nf, 6], dtype=torch.float64, device=dev)
+            N.check(N.lib().rh_array_solve_stats_ext(ctx, arr, m * nf, nf, m, N.ptr(prep["design"]), N.ptr(res["B_drag"]),
+                                                     N.ptr(K), 36 * nf * nf, N.ptr(X), float(self.fowtList[0].dw),
+                                                     N.ptr(psd), N.ptr(std), s), "rh_array_solve_stats_ext")
+            parts.append({"Xi": X, "iters": res["iters"].view(m, nf).clone(), "status": res["status"].view(m, nf).clone(),
+                          "zeta": res["zeta"].view(m, nf, nw)[:, 0].clone(), "psd": psd.view(m, nf, 6, nw),
+                          "std": std.view(m, nf, 6)})
+            torch.cuda.synchronize(dev)                   # the chunk's tables are released below
+            del res, dds, prep, arr, K
+        for f, fowt in enumerate(self.fowtList):
+            fowt.setPosition(X_ref[f])
+            fowt._dd = fowt._host = None
+        out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]} if parts else {}
+        if n:
+            out["mean_offsets"], out["statics_iters"], out["statics_status"] = sb["X"], sb["iters"], sb["status"]
+            if sb["J_moor"] is not None:      # array_mooring: amplitudes J_moor Xi, PSD over w[0] as the reference has it
+                Xi, J = out["Xi"], sb["J_moor"]
+                a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2
+                out["Tmoor_PSD"] = 0.5 * a2 / float(self.w[0])
+                out["Tmoor_std"] = torch.sqrt(0.5 * a2.sum(dim=2))
+                out["Tmoor_avg"] = sb["Tmoor_avg"]
+                out["Tmoor_max"] = out["Tmoor_avg"] + 3 * out["Tmoor_std"]
+                out["Tmoor_min"] = out["Tmoor_avg"] - 3 * out["Tmoor_std"]
+        return {k: v.cpu().numpy() for k, v in out.items()} if host else out
 
     def _array_extra_sea_states(self, P, res, X, out, keep):
         """Step 3 of analyzeArrayBatch: the further sea states of every case (one excitation and

@@ -1,0 +1,151 @@
+// Host build of rh_moor_array.h for the CPU check against raft/mooring.py and Model.solveStatics
+// (tests/test_moor_array_host.py): the same general line solve, free-point equilibrium, body
+// assembly, condensation and N-FOWT Newton the device runs, with every line taken in turn.
+// With -DMOOR_ARRAY_MAIN it is a stand-alone program (for a sanitizer run of the header) that
+// evaluates a two-body shared-mooring farm and a chain of 8 free points.
+#include <vector>
+
+#include "../raft-teststuff_amd/csrc/rh_moor_array.h"
+
+namespace {
+
+// the host execution policy: all lines in turn, one "lane" that is the leader
+struct HostEx {
+  int lbeg, lend;
+  int sbeg, sstep;
+  bool leader;
+  void sync() const {}
+};
+
+// rec_i: nb, np, nl, nf, free_sys;  rec_d: g, rho, free_tol, free_depth
+rh::moor::ArrSys make_sys(const int* rec_i, const double* rec_d, const double* pt, const double* ln) {
+  rh::moor::ArrSys S;
+  S.nb = rec_i[0], S.np = rec_i[1], S.nl = rec_i[2], S.nf = rec_i[3], S.free_sys = rec_i[4];
+  S.g = rec_d[0], S.rho = rec_d[1], S.free_tol = rec_d[2], S.free_depth = rec_d[3];
+  S.pt = pt, S.ln = ln;
+  return S;
+}
+
+}  // namespace
+
+// out [21]: fA[3], fB[3], Ku[9], TA, TB, HF, VF, iterations, status
+extern "C" void rh_moor_aline_host(const double* A, const double* B, double L, double EA, double W, double depth,
+                                   double tol, double HF0, double VF0, double* out) {
+  rh::moor::ALineSol s;
+  rh::moor::arr_line_solve(A[0], A[1], A[2], B[0], B[1], B[2], L, EA, W, depth, tol, HF0, VF0, true, s);
+  for (int i = 0; i < 3; ++i) out[i] = s.fA[i], out[3 + i] = s.fB[i];
+  for (int i = 0; i < 9; ++i) out[6 + i] = s.Ku[i];
+  out[15] = s.TA, out[16] = s.TB, out[17] = s.HF, out[18] = s.VF, out[19] = s.iters, out[20] = s.status;
+}
+
+// rh_moor_array_eval of one record at npose poses [npose][nb][6]; warm [npose][nl][2] and fre
+// [npose][nf][3] in/out; F [npose][6nb], K [npose][6nb][6nb], T [npose][2nl], J [npose][2nl][6nb] or null
+extern "C" void rh_moor_array_eval_host(const int* rec_i, const double* rec_d, const double* pt, const double* ln,
+                                        int npose, const double* poses, double* warm, double* fre, double* F, double* K,
+                                        double* T, double* J, int* nev, int* status) {
+  const rh::moor::ArrSys S = make_sys(rec_i, rec_d, pt, ln);
+  const int nD = 6 * S.nb, nF = 3 * S.nf;
+  std::vector<double> buf(rh::moor::arr_ws_doubles(nD, nF, S.nl));
+  rh::moor::ArrWs w;
+  rh::moor::arr_ws_carve(buf.data(), nD, nF, S.nl, w);
+  const HostEx ex{0, S.nl, 0, 1, true};
+  for (long p = 0; p < npose; ++p)
+    rh::moor::arr_eval_pose(S, ex, w, true, true, 0, nD, S.nl, S.nf, poses + p * nD, warm + p * 2 * S.nl, fre + p * nF,
+                            F + p * nD, K + p * nD * nD, T + p * 2 * S.nl, J ? J + p * 2 * S.nl * nD : nullptr, nev + p,
+                            status + p);
+}
+
+// rh_array_statics_solve of one case
+extern "C" void rh_array_statics_solve_host(const int* rec_i, const double* rec_d, const double* pt, const double* ln,
+                                            const double* X_ref, const double* K_hs, const double* F_const,
+                                            const double* warm0, const double* free0, double* X, double* warm, double* fre,
+                                            int* iters, int* status) {
+  const rh::moor::ArrSys S = make_sys(rec_i, rec_d, pt, ln);
+  const int nD = 6 * S.nb, nF = 3 * S.nf;
+  std::vector<double> buf(rh::moor::arr_ws_doubles(nD, nF, S.nl));
+  rh::moor::ArrWs w;
+  rh::moor::arr_ws_carve(buf.data(), nD, nF, S.nl, w);
+  const HostEx ex{0, S.nl, 0, 1, true};
+  rh::moor::arr_statics_case(S, ex, w, true, true, 0, nD, S.nl, S.nf, X_ref, K_hs, F_const, warm0, free0, X, warm, fre,
+                             iters, status);
+}
+
+#ifdef MOOR_ARRAY_MAIN
+#include <stdio.h>
+
+namespace {
+
+struct Tables {
+  std::vector<double> pt, ln;
+  int np, nl;
+};
+
+// points: {kind, index, x, y, z, m, v}; lines: {A, B, L, EA, W, depth, tol, sys}
+Tables tables(const std::vector<std::vector<double>>& points, const std::vector<std::vector<double>>& lines) {
+  Tables t;
+  t.np = (int)points.size(), t.nl = (int)lines.size();
+  t.pt.resize(rh::moor::kPtCount * t.np);
+  t.ln.resize(rh::moor::kLnCount * t.nl);
+  for (int i = 0; i < t.np; ++i)
+    for (int f = 0; f < rh::moor::kPtCount; ++f) t.pt[f * t.np + i] = points[i][f];
+  for (int i = 0; i < t.nl; ++i)
+    for (int f = 0; f < rh::moor::kLnCount; ++f) t.ln[f * t.nl + i] = lines[i][f];
+  return t;
+}
+
+int run(const char* name, int nb, int nf, const Tables& t, const std::vector<double>& pose, std::vector<double> fre,
+        double depth) {
+  const int rec_i[5] = {nb, t.np, t.nl, nf, 0};
+  const double rec_d[4] = {9.81, 1025.0, 0.05, depth};
+  const int nD = 6 * nb;
+  std::vector<double> warm(2 * t.nl, 0.0), F(nD), K(nD * nD), T(2 * t.nl), J(2 * t.nl * nD);
+  int nev = 0, st = 0;
+  rh_moor_array_eval_host(rec_i, rec_d, t.pt.data(), t.ln.data(), 1, pose.data(), warm.data(), fre.data(), F.data(),
+                          K.data(), T.data(), J.data(), &nev, &st);
+  printf("%s: status %d, %d line passes, F0 = %.6e, K00 = %.6e, T0 = %.6e, J00 = %.6e\n", name, st, nev, F[0], K[0], T[0],
+         J[0]);
+  // the mean-offset Newton with a soft restoring matrix and no constant load
+  std::vector<double> Khs(36 * nb, 0.0), Fc(6 * nb, 0.0), X(nD), fr2(fre);
+  for (int b = 0; b < nb; ++b)
+    for (int i = 0; i < 6; ++i) Khs[36 * b + 7 * i] = i < 3 ? 1.0e5 : 1.0e9;
+  int it = 0;
+  std::fill(warm.begin(), warm.end(), 0.0);
+  rh_array_statics_solve_host(rec_i, rec_d, t.pt.data(), t.ln.data(), pose.data(), Khs.data(), Fc.data(), nullptr,
+                              fre.data(), X.data(), warm.data(), fr2.data(), &it, &st);
+  printf("%s: Newton status %d after %d evaluations, X0 = %.6f\n", name, st, it, X[0]);
+  return st;
+}
+
+}  // namespace
+
+int main() {
+  const double w_rope = (15.28 - 1025.0 * M_PI / 4.0 * 0.1187 * 0.1187) * 9.81, EA = 9.702e7, D = 600.0, tol = 1e-5;
+  // two turbines 1600 m apart sharing a line with two clump weights, two anchor lines each
+  const Tables farm = tables(
+      {{1, 0, 58, 0, -14, 0, 0}, {2, 0, 200, 0, -65, 1e5, 0}, {2, 1, 1400, 0, -65, 1e5, 0}, {1, 1, -58, 0, -14, 0, 0},
+       {0, 0, -800, 800, -600, 0, 0}, {1, 0, -29, 50.229, -14, 0, 0}, {0, 0, -800, -800, -600, 0, 0},
+       {1, 0, -29, -50.229, -14, 0, 0}, {0, 0, 2400, 800, -600, 0, 0}, {1, 1, 29, 50.229, -14, 0, 0},
+       {0, 0, 2400, -800, -600, 0, 0}, {1, 1, 29, -50.229, -14, 0, 0}},
+      {{0, 1, 150, EA, w_rope, D, tol, 0}, {1, 2, 1168, EA, w_rope, D, tol, 0}, {2, 3, 150, EA, w_rope, D, tol, 0},
+       {4, 5, 1200, EA, w_rope, D, tol, 0}, {6, 7, 1200, EA, w_rope, D, tol, 0}, {8, 9, 1200, EA, w_rope, D, tol, 0},
+       {10, 11, 1200, EA, w_rope, D, tol, 0}});
+  int bad = run("farm", 2, 2, farm, {3, 1, -0.5, 0.01, 0.02, 0.03, 1604, -2, -0.4, -0.01, 0.02, -0.02},
+                {200, 0, -65, 1400, 0, -65}, D);
+  // anchor - 8 free clumps - fairlead of one body in 600 m, and a plain anchor line opposite
+  const double w_r = (40.0 - 1025.0 * M_PI / 4.0 * 0.12 * 0.12) * 9.81, w_c = (500.0 - 1025.0 * M_PI / 4.0 * 0.2 * 0.2) * 9.81;
+  std::vector<std::vector<double>> pts = {{0, 0, 800, 0, -600, 0, 0}}, lns;
+  std::vector<double> fre;
+  for (int i = 0; i < 8; ++i) {
+    const double x = 800.0 - 750.0 / 9 * (i + 1), z = -600.0 + 65.0 * (i + 1);
+    pts.push_back({2, (double)i, x, 0, z, 1000, 0});
+    fre.insert(fre.end(), {x, 0, z});
+  }
+  pts.push_back({1, 0, 50, 0, -15, 0, 0});
+  pts.push_back({0, 0, -800, 0, -600, 0, 0});
+  pts.push_back({1, 0, -50, 0, -15, 0, 0});
+  for (int i = 0; i < 9; ++i) lns.push_back({(double)i, (double)(i + 1), 112, 1e8, w_r, D, tol, 0});
+  lns.push_back({10, 11, 1000, 1e9, w_c, D, tol, 0});
+  bad += run("chain", 1, 8, tables(pts, lns), {0, 0, 0, 0, 0, 0}, fre, D);
+  return bad ? 1 : 0;
+}
+#endif
