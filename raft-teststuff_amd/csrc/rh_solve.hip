@@ -72,6 +72,9 @@ constexpr int kAxC = 4;               // axial wave-table rows phase C holds at 
 #define RH_JOINT_C 1                  // 1: k_solve_lds<2, 512> forms both bins' excitation in one phase-C node sweep
 #endif
 constexpr bool kJointC = RH_JOINT_C != 0;
+#ifndef RH_BATCH_B
+#define RH_BATCH_B 1                  // 1: phase B reads its LDS operands in batches ahead of their uses; 0: one by one (A/B)
+#endif
 #ifndef RH_JOINT_PARK
 #define RH_JOINT_PARK 1               // 1: bin 1's excitation waits in global memory for bin 0's solve; 0: in registers (A/B)
 #endif
@@ -92,6 +95,11 @@ constexpr int kGhost = 1;
 #ifndef RH_LDS_LANE_BRANCH
 #define RH_LDS_LANE_BRANCH 0          // 1: the round-2 per-lane `continue` before the solve (A/B only)
 #endif
+
+// |a|^2 as fma(re, re, im im), said outright.  Left to the compiler (abs2), which of the two products is
+// fused follows from the order of the sum's operands in its graph, and an unrelated change in phase B
+// swapped it in the PSD and RMS sums of the rotations ("Phase B's LDS chains").
+__device__ __forceinline__ double abs2_re(cd a) { return __builtin_fma(a.r, a.r, a.i * a.i); }
 
 // A scalar zero the compiler cannot fold (see its use in phase C).
 __device__ __forceinline__ int opaque_zero() {
@@ -285,6 +293,37 @@ __device__ __forceinline__ double t3to6_block(const double* Bm, double rx, doubl
   return blk == 0 ? b0 : blk == 1 ? b1 : b2;
 }
 
+// Entry (i, j) of translateMatrix3to6DOF(Bm, r), t3to6's sums (rh_common.h) with every multiply-add said
+// outright, for phase B's entries from a node's Bmat in registers.  Written as sums of products, which
+// product of a·b + c·d the compiler fuses follows from how many uses each has, and with one set of nine
+// values for all 36 entries the entries share products: other roundings than those of the entries
+// formed one by one from the LDS row.  These are the multiply-adds of that form, read from its assembly
+// ("Phase B's LDS chains"): the minuend of a difference is the fused product, else the
+// first one.  One exception is kept for the bits: (H Bm)[2][1] had its other product fused in the entries
+// (5, 3) and (5, 4), where the product was shared with a neighbour (`alt`).
+__device__ __forceinline__ double t3to6_fma(const double (&B)[9], double rx, double ry, double rz, int i, int j) {
+  auto fma = [](double a, double b, double c) { return __builtin_fma(a, b, c); };
+  auto bh = [&](int a, int c) {   // (Bm H)[a][c], H = [[0, rz, -ry], [-rz, 0, rx], [ry, -rx, 0]]
+    const double b0 = B[3 * a], b1 = B[3 * a + 1], b2 = B[3 * a + 2];
+    return c == 0 ? fma(b2, ry, fma(b0, 0.0, -(b1 * rz)))
+         : c == 1 ? fma(b2, -rx, fma(b0, rz, b1 * 0.0))
+                  : fma(b2, 0.0, fma(b1, rx, -(b0 * ry)));
+  };
+  auto hb = [&](int a, int k, bool alt) {   // (H Bm)[a][k]
+    const double b0 = B[k], b1 = B[3 + k], b2 = B[6 + k];
+    return a == 0 ? fma(-ry, b2, fma(0.0, b0, b1 * rz))
+         : a == 1 ? fma(rx, b2, fma(0.0, b1, -(b0 * rz)))
+                  : fma(0.0, b2, alt ? fma(-b1, rx, b0 * ry) : fma(b0, ry, -(b1 * rx)));
+  };
+  if (i < 3 && j < 3) return B[3 * i + j];
+  if (i < 3) return bh(i, j - 3);
+  if (j < 3) return bh(j, i - 3);
+  const int a = i - 3, c = j - 3;   // (H Bm H^T)[a][c] = sum_k (H Bm)[a][k] H[c][k], from 0 in k order
+  const double h0 = c == 0 ? 0.0 : c == 1 ? -rz : ry, h1 = c == 0 ? rz : c == 1 ? 0.0 : -rx;
+  const double h2 = c == 0 ? -ry : c == 1 ? rx : 0.0;
+  return fma(hb(a, 2, false), h2, fma(hb(a, 1, a == 2 && c < 2), h1, fma(hb(a, 0, false), h0, 0.0)));
+}
+
 // Every table the loops read is staged here: a global load inside the node loops would share
 // the vector-memory counter with the prefetched wave-table loads and force them to drain.
 __host__ __device__ inline size_t solve_lds_smem(int nn, int nm, int NB, int LT = kLT, bool ser = false, int NP = 1) {
@@ -321,6 +360,11 @@ template <int NB, int LT = kLT, bool SER = false, int NP = 1>
 __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(CaseArgs a) {
   constexpr bool JC = kJointC && NB == 2 && LT == kLT && !SER && NP == 1;
   constexpr int LW = LT / 64;
+  // Phase B with its LDS operands read ahead of their uses: a node's wave partials, its Bmat (kept in
+  // registers for the translate entries) and the node sum of B_drag (the non-SER kernels; the SER kernel
+  // keeps its own forms)
+  constexpr bool kBatchS = RH_BATCH_B != 0 && !SER;
+  constexpr int kSumB = 16;                        // per-node B_drag entries read per batch of phase B's node sum
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wv_s = __builtin_amdgcn_readfirstlane(wv);   // wave index in an SGPR
@@ -399,11 +443,25 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
                                                      // [2]: it + 1 once a test of iteration it failed,
                                                      // [3 + (it & 1)]: waves done with phase C of iteration it
   load_mbc(d, mbc, tid);
-  for (int n = tid; n < nn; n += LT) {
-    nt[n] = node[RH_NF_T * nn + n];
-    const double aq = node[RH_NF_AQ * nn + n], cdq = node[RH_NF_CDQ * nn + n];
-    const double ae = node[RH_NF_AEND * nn + n], cde = node[RH_NF_CDEND * nn + n];
-    ax[12 * n + 10] = (a.all_axial || aq * cdq != 0.0 || ae * cde != 0.0) ? 1 : 0;
+  for (int n = tid; n < nn; n += LT) nt[n] = node[RH_NF_T * nn + n];
+  // The flags and the list, by wave 0 alone, 64 nodes at a time: the chunk's flags as a ballot, a node's
+  // rank as the axial nodes of earlier chunks plus the flags below its lane.  One wave's LDS writes stay
+  // in order and the list's entries (k < count) and its padding (k >= count) are different words, so
+  // the barrier that ends the prologue is the only one this needs.
+  if (wv_s == 0) {
+    int nq = 0;   // uniform: axial nodes so far
+    for (int n0 = 0; n0 < nn; n0 += 64) {
+      const int n = n0 + lane, nc = n < nn ? n : nn - 1;
+      const double aq = node[RH_NF_AQ * nn + nc], cdq = node[RH_NF_CDQ * nn + nc];
+      const double ae = node[RH_NF_AEND * nn + nc], cde = node[RH_NF_CDEND * nn + nc];
+      const bool f = n < nn && (a.all_axial || aq * cdq != 0.0 || ae * cde != 0.0);
+      const unsigned long long mask = __ballot(f);
+      const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+      if (n < nn) ax[12 * n + 10] = f ? 1 : 0;
+      if (f) ax[12 * (nq + below) + 11] = n;
+      nq += __popcll(mask);
+    }
+    for (int k = nq + lane; k < nn; k += 64) ax[12 * k + 11] = -1;
   }
   for (int e = tid; e < 18 * nm; e += LT) mbf[e] = d.memb[(e % 18) * nm + e / 18];   // RH_MF_CQ0..C20: fields 0..17
   // (the last member's end is never met by a node index: ghost nodes open or close no member)
@@ -480,18 +538,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   // closest call of the convergence test (rh_solve_out.margin); pass 2 continues pass 1's
   double margin = resume && a.o.margin ? a.o.margin[ic] : INFINITY;
   const int itend = resume || stop_iter >= nloop ? nloop : stop_iter;
-  __syncthreads();
-  for (int n = tid; n < nn; n += LT) {   // the list: node n goes to the entry of its rank
-    int rank = 0, nq = 0;
-    for (int k = 0; k < nn; ++k) {
-      const int f = ax[12 * k + 10] & 1;
-      nq += f;
-      rank += k < n ? f : 0;
-    }
-    if (ax[12 * n + 10] & 1) ax[12 * rank + 11] = n;
-    if (n >= nq) ax[12 * n + 11] = -1;
-  }
-  __syncthreads();
   __syncthreads();
   PROF_T(tp1);
   PROF_ADD(0, tp1 - tp0);
@@ -1044,7 +1090,12 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     PROF_T(ta1);
     PROF_ADD(1, ta1 - ta0);
     // ---------------- B: node drag matrices and B_drag ----------------------------------
-    for (int n = tid; n < nn; n += LT) {
+    // (the batched form indexes with the thread's number formed anew, here and in the node sum below: the
+    // LDS addresses that follow from a hoisted copy are computed once before the iteration loop and stay
+    // live across the solve, where two more of them cost the kernel a 256th VGPR and the one-bin kernels
+    // four more spilled ones)
+    const int tid_b = kBatchS ? wv_s * 64 + lane_here() : tid;
+    for (int n = tid_b; n < nn; n += LT) {
       // the node's fields XX .. CIRC and T, all loads issued before any use (left to the
       // scheduler, each load waited on before the next was issued: eight serial L2 round trips)
       double fv[RH_NF_CIRC - RH_NF_XX + 2];
@@ -1054,13 +1105,32 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       __builtin_amdgcn_sched_barrier(0);
       auto F = [&](int f) { return f == RH_NF_T ? fv[RH_NF_CIRC - RH_NF_XX + 1] : fv[f - RH_NF_XX]; };
       double r3[3];
+      if constexpr (kBatchS) {
+        // the 3 LW wave partials, every read issued before the first add (left to the scheduler, each
+        // pair of partials was read, waited for and added in turn: 12 serial LDS round trips at LW = 8);
+        // summed in wave order as before, while the field loads above are still in flight
+        double pr[3][LW];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double* R = red + (size_t)(n * 3 + c) * LW;
-        double s = 0;
+        for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int w = 0; w < LW; ++w) s += R[w];
-        r3[c] = s;
+          for (int w = 0; w < LW; ++w) pr[c][w] = red[(size_t)(n * 3 + c) * LW + w];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          double s = 0;
+#pragma unroll
+          for (int w = 0; w < LW; ++w) s += pr[c][w];
+          r3[c] = s;
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const double* R = red + (size_t)(n * 3 + c) * LW;
+          double s = 0;
+#pragma unroll
+          for (int w = 0; w < LW; ++w) s += R[w];
+          r3[c] = s;
+        }
       }
       // a node that does not need its axial sum has none (phase A wrote no partials for it): an
       // exact 0, so vq = 0 and Bq = Be = +0, the zeros that its zero coefficients give anyway
@@ -1071,7 +1141,18 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       const bool circ = F(RH_NF_CIRC) != 0.0;
       const double sums[3] = {r3[0] * qq, circ ? r3[1] * pp1 + r3[2] * pp2 : r3[1] * pp1, r3[2] * pp2};
       double B4[4];
-      node_bmat_f(F, rho, sums, bm + 9 * n, B4);
+      // The node's Bmat stays in registers for the 36 translate entries below.  Read back from the LDS
+      // row, every entry's operands were loaded anew behind the stores of the entries before it and waited
+      // for with a full drain (the stores to bdn, a double* into the same array, may alias bm for all the
+      // compiler knows): 73 drains per node.  The row is still written, for the epilogue's Bmat output.
+      double Bn[9];
+      if constexpr (kBatchS) {
+        node_bmat_f(F, rho, sums, Bn, B4);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) bm[9 * n + k] = Bn[k];
+      } else {
+        node_bmat_f(F, rho, sums, bm + 9 * n, B4);
+      }
       const double t = F(RH_NF_T);
       double* A = al + 6 * n;
       A[0] = B4[0] + B4[3];     // axial: side + end   (qMat terms of Bmat, raft/raft_fowt.py:1228-1248)
@@ -1083,7 +1164,8 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         // this node's translateMatrix3to6DOF (raft/helpers.py:455-478), summed below in node order
         const double rx = F(RH_NF_XX), ry = F(RH_NF_XY), rz = F(RH_NF_XZ);
 #pragma unroll
-        for (int e = 0; e < 36; ++e) bdn[e * nn + n] = t3to6(bm + 9 * n, rx, ry, rz, e / 6, e % 6);
+        for (int e = 0; e < 36; ++e)
+          bdn[e * nn + n] = kBatchS ? t3to6_fma(Bn, rx, ry, rz, e / 6, e % 6) : t3to6(bm + 9 * n, rx, ry, rz, e / 6, e % 6);
       }
     }
     __syncthreads();
@@ -1121,8 +1203,36 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       if (tid < 36) bsum[tid] = mbc[36 + tid] + bd[tid];
     } else if (tid < 36) {
       double s = 0;
-      const double* P = bdn + tid * nn;
-      for (int n = 0; n < nn; ++n) s += P[n];
+      // (tid < 36: wave 0, lane = tid.  The lane formed anew: the batched form reads from two addresses
+      // that follow from tid, which are computed once before the iteration loop and stay live across the
+      // solve; with tid itself the kernel took one VGPR more.)
+      const double* P = bdn + (kBatchS ? lane_here() : tid) * nn;
+      if constexpr (kBatchS) {
+        // kSumB nodes' entries read before their adds, the adds strictly in node order (the plain loop
+        // ran as one LDS round trip per two nodes).  The last batch reads kSumB - 1 words from its first
+        // node on and adds those of the nodes there are: the words past the row belong to the next entry's
+        // row or, behind the last row, to nt and lw (at least 128 doubles), so they are inside the block.
+        int n = 0;
+        for (; n + kSumB <= nn; n += kSumB) {
+          double p[kSumB];
+#pragma unroll
+          for (int k = 0; k < kSumB; ++k) p[k] = P[n + k];
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = 0; k < kSumB; ++k) s += p[k];
+        }
+        if (n < nn) {
+          double p[kSumB - 1];
+#pragma unroll
+          for (int k = 0; k < kSumB - 1; ++k) p[k] = P[n + k];
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int k = 0; k < kSumB - 1; ++k)
+            if (n + k < nn) s += p[k];
+        }
+      } else {
+        for (int n = 0; n < nn; ++n) s += P[n];
+      }
       bd[tid] = s;
       bsum[tid] = mbc[36 + tid] + s;   // the B_lin + B_drag of every bin's Z (same sum as before)
     }
@@ -1329,7 +1439,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           const double rz = fabs(z) > 1e-6 ? 1.0 / z : 0.0;
           double m2v[6];
 #pragma unroll
-          for (int c = 0; c < 6; ++c) m2v[c] = okj ? abs2(c >= 3 ? scl(F[c], kRad2Deg) : F[c]) : 0.0;
+          for (int c = 0; c < 6; ++c) m2v[c] = okj ? abs2_re(c >= 3 ? scl(F[c], kRad2Deg) : F[c]) : 0.0;
           if (okj) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) {

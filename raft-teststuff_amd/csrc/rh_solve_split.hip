@@ -9,6 +9,7 @@
 // form sits in the other's code, and the default kernel keeps its name in profiles and in
 // tools/isa_check.py.  Built with rh_solve_fast.hip's flags (__graft_entry__.py UNITS).
 #define RH_JOINT_C 0
+#define RH_BATCH_B 0   // phase B in its plain form too: the cross-check then covers the default's batched reads
 #define k_solve_lds k_solve_lds_split
 #include "rh_solve.hip"
 #undef k_solve_lds

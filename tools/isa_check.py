@@ -18,6 +18,9 @@ checks every kernel:
     (ring depth - 1) x loads per slot outstanding (`ringA=`, `ringC=`) -> FAIL below that; the joint
     phase-C loop of the C2 kernel (both bins of a thread per node step) has its own line, `ringCJ=`;
   * the compiler's VGPR and spilled-VGPR counts of every kernel (`vgpr=`, `spill=`), reported.
+  * for the C2 kernel, the `s_waitcnt lgkmcnt` count of phase B (`phaseB_lgkm_waits=`): the section runs on
+    one wave while seven wait, so its dependent LDS round trips are step time; reported (tests/test_isa_phase_b.py
+    gates it).
 Loops are found from the branch structure: a branch to a label that precedes it closes a loop
 [label, branch]; a loop that contains no other loop is innermost; it streams if it holds a
 buffer_load / global_load.
@@ -215,6 +218,30 @@ def ring_gate(rings):
     return out
 
 
+BARRIER = re.compile(r"^\s*s_barrier\b")
+LGKM_WAIT = re.compile(r"^\s*s_waitcnt\s.*lgkmcnt\(")
+FIELD_LOAD = re.compile(r"^\s*global_load_dwordx2\b")
+
+
+def phase_b_lgkm_waits(body):
+    """`s_waitcnt lgkmcnt` instructions of phase B of a k_solve_lds body: every one is a point at which
+    the one working wave may stand still for an LDS round trip (or a scalar load) while the others wait at
+    the barrier.  Phase B is found from its shape: its node loop loads the node's 20-odd fields
+    (global_load_dwordx2) between the barrier that closes phase A and the barrier before the node sum,
+    the only stretch between two barriers with that many; the barrier after the next one closes phase B.
+    None: no such stretch."""
+    bars = [i for i, ln in enumerate(body) if BARRIER.match(ln)]
+    best = None
+    for k in range(len(bars) - 2):
+        n = sum(1 for i in range(bars[k], bars[k + 1]) if FIELD_LOAD.match(body[i]))
+        if n >= 16 and (best is None or n > best[0]):
+            best = (n, k)
+    if best is None:
+        return None
+    k = best[1]
+    return sum(1 for i in range(bars[k], bars[k + 2]) if LGKM_WAIT.match(body[i]))
+
+
 def analyse(body):
     labels = {}
     for i, ln in enumerate(body):
@@ -294,6 +321,9 @@ def main():
                            f"{'not found' if low is None else low} < {need}")
         vg, sp = res.get(name, (None, None))
         rings += f" vgpr={'?' if vg is None else vg} spill={'?' if sp is None else sp}"
+        if any(k in dn for k in JOINT_C):
+            nb = phase_b_lgkm_waits(body)
+            rings += f" phaseB_lgkm_waits={'?' if nb is None else nb}"
         if verdict.startswith("FAIL"):
             fails.append(dn)
         rows.append(f"{dn:70s} hot={int(hot)} loops={r['loops']:3d} inner={r['inner']:3d} "
