@@ -395,6 +395,53 @@ int rh_array_statics_solve(rh_ctx* ctx, const rh_moor_array_system* sys, const r
                            const double* warm0, const double* free0, double* X, double* warm, double* free_pts,
                            int* iters, int* status, rh_stream stream);
 
+/* ---- rotor blade-element momentum loads (csrc/rh_rotor.h, rh_rotor.hip) ----
+ * The device form of raft/ccblade.py's CCBlade.evaluate (iterRe = 1, airfoils with one Reynolds
+ * number): one workgroup per operating point, one lane per (sector, section); the sections of a
+ * sector sit in adjacent lanes of a group of the next power of two >= the largest nr, at most 64.
+ * Underwater rotors, cavitation and the coefficient outputs are not covered. */
+enum rh_rotor_section_field {
+  RH_RS_R, RH_RS_CHORD,               /* station radius and chord [m] */
+  RH_RS_THETA,                        /* twist [rad] */
+  RH_RS_XAZ, RH_RS_YAZ, RH_RS_ZAZ,    /* define_curvature of the blade stations [m] */
+  RH_RS_CONE,                         /* ... and its local cone angle [rad] (the inflow's) */
+  RH_RS_WEIGHT,                       /* trapezoid weight 0.5 (ds[i-1] + ds[i]) on the path hub, stations, tip [m] */
+  RH_RS_CONE_PATH,                    /* the cone angle of that full path at the station [rad] (thrust_torque's) */
+  RH_RS_COUNT
+};
+#define RH_ROTOR_MAX_SECTIONS 64
+#define RH_ROTOR_MAX_SECTORS 16
+#define RH_ROTOR_MAX_KNOTS 128 /* alpha knots of one polar spline */
+
+typedef struct {
+  int nr, nsector, B;                         /* blade stations, azimuthal sectors, blades */
+  int usecd, tiploss, hubloss, wakerotation;  /* CCBlade's bemoptions */
+  int kx;                                     /* degree of the polar splines in alpha, 1..3 (degree 1 in Re, 4 knots) */
+  int knot_stride;                            /* row length of the knot table, the largest knot count .. RH_ROTOR_MAX_KNOTS */
+  int pad_;
+  double Rhub, Rtip, rho, mu, precone, hubHt, shearExp;
+  const double* section;       /* device [RH_RS_COUNT][nr], struct of arrays */
+  const int* nknot;            /* device [2][nr]: alpha knot count of each station's cl (row 0) and cd (row 1) spline */
+  const double* knots;         /* device [2][nr][knot_stride + 4]: the alpha knots, padded, then the 4 Re knots */
+  const double* coef;          /* device [2][nr][knot_stride][2]: (nknot - kx - 1) rows of 2 coefficients, padded */
+  const double* section_host;  /* the same four tables in host memory: validated before the launch */
+  const int* nknot_host;
+  const double* knots_host;
+  const double* coef_host;
+} rh_rotor;
+
+/* Hub loads of npoint operating points.  rot: HOST array of nrot records, validated here; rot_dev:
+ * the same records in device memory.  rot_idx: device [npoint] or NULL (every point uses rotor 0).
+ * op: device [npoint][5] = Uinf [m/s], Omega [rpm], pitch [deg], tilt [rad], yaw [rad].  loads
+ * [npoint][8] = T, Y, Z, Q, My, Mz, Mb, P.  dloads [npoint][2][3] = d(T, Q)/d(Uinf, Omega, pitch) in
+ * those units (CCBlade's central differences at the converged phi), or NULL: no derivative work.
+ * sec [npoint][ns_max][nr_max][3] = phi, Np, Tp of every (sector, section), ns_max / nr_max the
+ * largest nsector / nr of rot[0..nrot), entries a rotor lacks written as zeros; or NULL.
+ * status: device [npoint]: 0 fine, 1 some section had no sign change in any bracket (phi = 0 there,
+ * as the host), 2 a non-finite load, 3 rot_idx out of range (the row's outputs are zeros). */
+int rh_rotor_loads(rh_ctx* ctx, const rh_rotor* rot, const rh_rotor* rot_dev, int nrot, int npoint, const int* rot_idx,
+                   const double* op, double* loads, double* dloads, double* sec, int* status, rh_stream stream);
+
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
  * (raft/raft_model.py:877-1013) including FOWT.calcHydroLinearization (raft/raft_fowt.py:

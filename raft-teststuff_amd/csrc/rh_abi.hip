@@ -448,6 +448,7 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
 }  // extern "C" (rh_moor.h has templates; the two calls take their linkage from rafthip.h)
 #include "rh_moor.hip"   // k_moor_eval, k_statics_solve + rh_moor_eval, rh_statics_solve (uses fail / RH_HIP above)
 #include "rh_moor_array.hip"   // k_moor_array_eval, k_array_statics_solve + their two ABI calls
+#include "rh_rotor.hip"        // k_rotor_loads + rh_rotor_loads
 extern "C" {
 
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,

@@ -98,6 +98,25 @@ MAL_COUNT = len(MOOR_ALINE_FIELDS)
 ARR_MAX_BODIES, ARR_MAX_FREE = 4, 8
 
 
+class RhRotor(ctypes.Structure):
+    _fields_ = [("nr", ctypes.c_int), ("nsector", ctypes.c_int), ("B", ctypes.c_int), ("usecd", ctypes.c_int),
+                ("tiploss", ctypes.c_int), ("hubloss", ctypes.c_int), ("wakerotation", ctypes.c_int),
+                ("kx", ctypes.c_int), ("knot_stride", ctypes.c_int), ("pad_", ctypes.c_int),
+                ("Rhub", ctypes.c_double), ("Rtip", ctypes.c_double), ("rho", ctypes.c_double), ("mu", ctypes.c_double),
+                ("precone", ctypes.c_double), ("hubHt", ctypes.c_double), ("shearExp", ctypes.c_double),
+                ("section", _p), ("nknot", _p), ("knots", _p), ("coef", _p),
+                ("section_host", _p), ("nknot_host", _p), ("knots_host", _p), ("coef_host", _p)]
+
+
+# section-table row order (enum rh_rotor_section_field) and the limits of rh_rotor_loads
+ROTOR_SECTION_FIELDS = ["R", "CHORD", "THETA", "XAZ", "YAZ", "ZAZ", "CONE", "WEIGHT", "CONE_PATH"]
+RS = {name: i for i, name in enumerate(ROTOR_SECTION_FIELDS)}
+RS_COUNT = len(ROTOR_SECTION_FIELDS)
+ROTOR_MAX_SECTIONS, ROTOR_MAX_SECTORS, ROTOR_MAX_KNOTS = 64, 16, 128
+ROTOR_STATUS = {0: "ok", 1: "a blade section without a sign change of the BEM residual in any bracket",
+                2: "non-finite rotor load", 3: "rotor index out of range"}
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -137,6 +156,8 @@ def lib():
                                        _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_array_statics_solve": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p,
                                            _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+                "rh_rotor_loads": [_p, ctypes.POINTER(RhRotor), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p,
+                                   _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,

@@ -287,12 +287,68 @@ class FOWT:
         self.D_hydro = D
         return D
 
-    def calcTurbineConstants(self, case, ptfm_pitch=0):
+    def _rotor_operates(self, ir, case):
+        """Whether calcTurbineConstants evaluates rotor ir's aerodynamics in this case."""
+        status = get_from_dict(case, "turbine_status", shape=0, dtype=str, default="operating")
+        if status != "operating":
+            return False
+        speed = get_from_dict(case, "wind_speed", shape=0, default=10.0)
+        mods = np.atleast_1d(self._aero_mod)
+        rot = self.rnaList[ir] if ir < len(self.rnaList) else None
+        mod = rot.aeroServoMod if isinstance(rot, Rotor) else mods[min(ir, len(mods) - 1)]
+        return bool(mod > 0 and speed > 0.0)
+
+    def rotorLoadsBatch(self, cases, device=0):
+        """The blade-element loads of every (case, rotor) that operates (turbine_status "operating",
+        aeroServoMod > 0, wind speed > 0) in one rh_rotor_loads launch (raft/rotor_device.py): each
+        operating point formed as Rotor.calcAero and runCCBlade form it (speed_gain, the schedule,
+        setYaw's tilt and yaw misalignment at the FOWT's current pose).  Returns one entry per case:
+        the `bem` argument of calcTurbineConstants, a list with a (loads, derivs) pair per rotor
+        (None for a rotor that does not operate).  A non-zero status raises RuntimeError."""
+        from . import _native as N
+        from .rotor_device import DeviceRotor, bem_pair
+        if self._rotor_submerged:
+            raise NotImplementedError("underwater rotors (raft/raft_rotor.py) are outside the accelerated path")
+        pairs = [(ic, ir) for ic, case in enumerate(cases) for ir in range(self.nrotors) if self._rotor_operates(ir, case)]
+        out = [[None] * self.nrotors for _ in cases]
+        if not pairs:
+            return out
+        rotors = sorted({ir for _, ir in pairs})
+        for ir in rotors:
+            if not isinstance(self.rnaList[ir], Rotor):
+                raise NotImplementedError("rotor aerodynamics need the turbine's blade, airfoil, operating-point "
+                                          "and control inputs (raft/raft_rotor.py:37-374)")
+        key = (device,) + tuple(id(self.rnaList[ir].ccblade) for ir in rotors)
+        if getattr(self, "_rotor_dev", None) is None or self._rotor_dev[0] != key:
+            self._rotor_dev = (key, DeviceRotor([self.rnaList[ir].ccblade for ir in rotors], device))   # refusals first
+        dr = self._rotor_dev[1]
+        op = np.zeros([len(pairs), 5])
+        idx = np.zeros(len(pairs), dtype=np.int32)
+        for n, (ic, ir) in enumerate(pairs):
+            rot, case = self.rnaList[ir], cases[ic]
+            speed = get_from_dict(case, "wind_speed", shape=0, default=10)
+            tilt, yaw = rot.inflow_angles(case)
+            op[n] = (*rot.operating_point(speed), tilt, yaw)
+            idx[n] = rotors.index(ir)
+        res = dr.launch(idx, op, derivatives=True)
+        status = res["status"].cpu().numpy()
+        if np.any(status):
+            n = int(np.flatnonzero(status)[0])
+            raise RuntimeError(f"rotorLoadsBatch: case {pairs[n][0]}, rotor {pairs[n][1]}: status {int(status[n])} "
+                               f"({N.ROTOR_STATUS.get(int(status[n]), '?')})")
+        L, D = res["loads"].cpu().numpy(), res["dloads"].cpu().numpy()
+        for n, (ic, ir) in enumerate(pairs):
+            out[ic][ir] = bem_pair(dr.flat[idx[n]].nr, L[n], D[n], op[n, 1])
+        return out
+
+    def calcTurbineConstants(self, case, ptfm_pitch=0, bem=None):
         """raft/raft_fowt.py:773-845: for every operating rotor with aeroServoMod > 0 at wind
         speed > 0, the aero-servo added mass, damping and wind excitation of Rotor.calcAero
         (raft/rotor.py; CCBlade evaluates the blades) moved from the hub to the platform
         reference point (translateMatrix6to6DOF / transformForce with r_hub_rel), the mean aero
-        loads f_aero0 and the rotor's gyroscopic damping B_gyro.  Host work: 6x6 per bin."""
+        loads f_aero0 and the rotor's gyroscopic damping B_gyro.  Host work: 6x6 per bin.
+        bem: one entry per rotor, a (loads, derivs) pair that stands in for that rotor's CCBlade
+        evaluation (an entry of rotorLoadsBatch's result), or None: the host evaluates."""
         status = get_from_dict(case, "turbine_status", shape=0, dtype=str, default="operating")
         had_aero = bool(np.any(self.A_aero) or np.any(self.B_aero) or np.any(self.B_gyro))
         self.A_aero = np.zeros([6, 6, self.nw, self.nrotors])
@@ -313,7 +369,7 @@ class FOWT:
                 if not isinstance(rot, Rotor):
                     raise NotImplementedError("rotor aerodynamics need the turbine's blade, airfoil, operating-point "
                                               "and control inputs (raft/raft_rotor.py:37-374)")
-                f0, f, a, b = rot.calcAero(case)
+                f0, f, a, b = rot.calcAero(case, bem=None if bem is None else bem[ir])
                 for iw in range(self.nw):
                     self.A_aero[:, :, iw, ir] = translate_matrix_6to6(a[:, :, iw], rot.r_hub_rel)
                     self.B_aero[:, :, iw, ir] = translate_matrix_6to6(b[:, :, iw], rot.r_hub_rel)

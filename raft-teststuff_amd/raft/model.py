@@ -352,7 +352,7 @@ class Model:
                       f"{fowt.Xi0[1]: .2f},  and heave = {fowt.Xi0[2]: .2f} m")
         return X
 
-    def _statics_batch_inputs(self, cases, F_extra=None):
+    def _statics_batch_inputs(self, cases, F_extra=None, rotor_device=False):
         """The host side of solveStaticsBatch: the device mooring system, X_ref [6], K_hs [6,6],
         F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref."""
         from .mooring_device import DeviceMooring, warm_state
@@ -377,9 +377,10 @@ class Model:
         F_und = fowt.W_struc + fowt.W_hydro
         warm0 = warm_state(fowt.ms)                      # the line solutions at the reference pose
         F_const = np.zeros([n, 6])
+        bems = fowt.rotorLoadsBatch([dict(c) for c in cases], self.device) if rotor_device else None
         for i, case in enumerate(cases):
             ci = dict(case)
-            fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+            fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i] if bems else None)
             F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
             if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
                 F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
@@ -388,7 +389,7 @@ class Model:
                 F_const[i] += np.asarray(F_extra[i], dtype=float)
         return dm, X_ref, K_hs, F_const, warm0
 
-    def solveStaticsBatch(self, cases, F_extra=None, host=True):
+    def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False):
         """The mean offsets of many load cases in two device launches (rh_statics_solve, then
         rh_moor_eval at the solved poses): solveStatics' Newton per case, every case's lines in
         adjacent lanes (csrc/rh_moor.hip).  A single FOWT with its own mooring system; F_extra
@@ -396,8 +397,10 @@ class Model:
         as solveStatics builds them.  Returns X [n,6], Xi0 [n,6], F_moor [n,6], C_moor [n,6,6],
         Tmoor_avg [n,2L], J_moor [n,2L,6], iters [n] (evaluations: len(Model.Xs2) of the host
         path) and status [n] (0 = converged, else _native.MOOR_STATUS); numpy arrays, or device
-        tensors with host=False.  The model is left at its reference pose."""
-        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra)
+        tensors with host=False.  The model is left at its reference pose.  rotor_device=True takes the
+        rotors' blade-element loads of all cases from one device launch (FOWT.rotorLoadsBatch) instead of
+        one host CCBlade evaluation per case; a case whose rotor solve fails raises RuntimeError."""
+        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, rotor_device)
         n = len(cases)
         sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)))
         ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True)
@@ -407,7 +410,7 @@ class Model:
                    F_moor=ev["F"], C_moor=ev["K"], Tmoor_avg=ev["T"], J_moor=ev["J"], iters=sol["iters"], status=status)
         return {k: v.cpu().numpy() for k, v in out.items()} if host else out
 
-    def _statics_array_inputs(self, cases, F_extra=None):
+    def _statics_array_inputs(self, cases, F_extra=None, rotor_device=False):
         """The host side of solveStaticsArrayBatch: the merged record and one record per system,
         X_ref [N,6], K_hs [N,6,6], F_const [n,N,6] and the state (line warm starts, free
         points) of every system with the FOWTs at their reference poses.  Every refusal is raised
@@ -443,12 +446,13 @@ class Model:
             self.ms.set_body_positions(list(X_ref))
         warm0, free0 = array_state(rec)                  # the state at the reference poses, read once
         F_const = np.zeros([n, nf, 6])
+        bems = self._array_rotor_loads(cases) if rotor_device else None
         for ic, case in enumerate(cases):
             for i, fowt in enumerate(self.fowtList):
                 ci = dict(case)
                 if isinstance(case.get("wind_speed"), list):
                     ci["wind_speed"] = case["wind_speed"][i]
-                fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+                fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i][ic] if bems else None)
                 fowt.calcHydroConstants()
                 F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
                 if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
@@ -458,7 +462,21 @@ class Model:
             F_const += np.asarray(F_extra, dtype=float).reshape(n, nf, 6)
         return rec, subs, X_ref, K_hs, F_const, warm0, free0
 
-    def solveStaticsArrayBatch(self, cases, F_extra=None, host=True):
+    def _array_rotor_loads(self, cases):
+        """FOWT.rotorLoadsBatch of every FOWT at its current pose, a per-FOWT wind-speed list of a
+        case read as the statics loops read it.  Returns [FOWT][case] bem arguments."""
+        out = []
+        for i, fowt in enumerate(self.fowtList):
+            cs = []
+            for case in cases:
+                ci = dict(case)
+                if isinstance(case.get("wind_speed"), list):
+                    ci["wind_speed"] = case["wind_speed"][i]
+                cs.append(ci)
+            out.append(fowt.rotorLoadsBatch(cs, self.device))
+        return out
+
+    def solveStaticsArrayBatch(self, cases, F_extra=None, host=True, rotor_device=False):
         """The mean offsets of many load cases of N >= 1 FOWTs moored by the array-level system and / or
         their own systems, in two device launches (rh_array_statics_solve on the merged record, then
         rh_moor_array_eval of every system at the solved poses): Model.solveStatics' Newton per case
@@ -471,9 +489,9 @@ class Model:
         system (None without one), Tmoor_avg_own / J_moor_own (per FOWT, [n,2Li] / [n,2Li,6] or None),
         iters [n] (evaluations: len(Model.Xs2) of the host path), status [n] (0 = converged, else
         _native.MOOR_STATUS); numpy arrays, or device tensors with host=False.  The model is left at
-        its reference pose."""
+        its reference pose.  rotor_device: as solveStaticsBatch, one launch per FOWT."""
         from .mooring_array_device import DeviceArrayMooring
-        rec, subs, X_ref, K_hs, F_const, warm0, free0 = self._statics_array_inputs(cases, F_extra)
+        rec, subs, X_ref, K_hs, F_const, warm0, free0 = self._statics_array_inputs(cases, F_extra, rotor_device)
         # the device records are kept between calls while the freshly flattened tables equal theirs
         dm = getattr(self, "_moor_arr_dev", None)
         if dm is None or dm.dev_index != self.device or not dm.same_tables(subs):
@@ -534,7 +552,7 @@ class Model:
         cpu = lambda v: None if v is None else v.cpu().numpy()   # noqa: E731
         return {k: [cpu(x) for x in v] if isinstance(v, list) else cpu(v) for k, v in out.items()}
 
-    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk):
+    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False):
         """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
         analyzeCases solves it when the mooring is a system.  Offsets, C_moor and the tension
         Jacobian of every case come from solveStaticsBatch; each case then gets its own
@@ -558,7 +576,9 @@ class Model:
         if any(len(s[0]) > 1 for s in seas):
             raise NotImplementedError("analyzeCasesBatch(statics=True): several sea states per case")
         self._calc_bem_once()
-        sb = self.solveStaticsBatch(cases, host=False)
+        sb = self.solveStaticsBatch(cases, host=False, rotor_device=rotor_device)
+        # (the model is at its reference pose here, where the loop below takes the turbine constants)
+        bems = fowt.rotorLoadsBatch([dict(c) for c in cases], self.device) if rotor_device else None
         X = sb["X"].cpu().numpy()
         C = sb["C_moor"].cpu().numpy()
         Fm = sb["F_moor"].cpu().numpy()
@@ -570,7 +590,7 @@ class Model:
             views = []
             for i in ids:
                 fowt.setPosition(X_ref)
-                fowt.calcTurbineConstants(dict(cases[i]), ptfm_pitch=0)
+                fowt.calcTurbineConstants(dict(cases[i]), ptfm_pitch=0, bem=bems[i] if bems else None)
                 fowt.calcHydroConstants()
                 fowt.setPosition(X[i])
                 fowt.C_moor, fowt.F_moor0 = C[i].copy(), Fm[i].copy()
@@ -740,7 +760,7 @@ class Model:
         return self.results
 
     def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
-                          pose_chunk=32):
+                          pose_chunk=32, rotor_device=False):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -764,11 +784,15 @@ class Model:
         per-case designs.  Added keys: mean_offsets [n,6], Tmoor_avg [n,2L], Tmoor_std [n,2L],
         Tmoor_PSD [n,2L,nw] (mooring_outputs' channels), statics_iters, statics_status.  One sea state
         per case; arrays, potSecOrder > 0 and a C_moor fixture raise NotImplementedError.
-        statics=False (the default) holds the platform at its reference position."""
+        statics=False (the default) holds the platform at its reference position.
+        rotor_device=True takes the blade-element loads of every case with an operating rotor from one
+        device launch (FOWT.rotorLoadsBatch) ahead of the per-case loop instead of one host CCBlade
+        evaluation per case; a case whose rotor solve fails raises RuntimeError.  The default changes
+        nothing."""
         if statics:
-            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk)
+            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device)
         if self.nFOWT != 1:
-            return self.analyzeArrayBatch(cases, tol=tol, host=host)
+            return self.analyzeArrayBatch(cases, tol=tol, host=host, rotor_device=rotor_device)
         fowt = self.fowtList[0]
         self._calc_bem_once()
         seas = [self._case_sea_states(c) for c in cases]
@@ -796,9 +820,13 @@ class Model:
         base = fowt.device_design()
         base.ensure_headings(np.unique(np.asarray(hd, dtype=float)) * DEG2RAD)
         views, idx = [base], np.zeros(len(cases), dtype=np.int32)
+        bems = {}
+        if rotor_device:
+            sel = [i for i in range(len(cases)) if aero[i]]
+            bems = dict(zip(sel, fowt.rotorLoadsBatch([dict(cases[i]) for i in sel], self.device)))
         for i, c in enumerate(cases):
             if aero[i]:
-                fowt.calcTurbineConstants(dict(c), ptfm_pitch=0)
+                fowt.calcTurbineConstants(dict(c), ptfm_pitch=0, bem=bems.get(i))
                 M, B, _, _ = linear_matrices(fowt)
                 f64 = dict(dtype=torch.float64, device=base.device)
                 views.append(CaseMB(base, torch.tensor(M, **f64).contiguous(), torch.tensor(B, **f64).contiguous()))
@@ -931,7 +959,7 @@ class Model:
                     K=None if Ka is None else torch.tensor(Ka, dtype=torch.float64, device=dev).contiguous())
 
     def analyzeArrayBatch(self, cases=None, tol=0.01, host=True, marks=None, prepared=None, statics=False,
-                          pose_chunk=32):
+                          pose_chunk=32, rotor_device=False):
         """The coupled-array response of many cases (raft/raft_model.py:852-1065 for nFOWT > 1)
         in a few device calls instead of per-case, per-FOWT host round trips:
           1. every (case, FOWT) drag fixed point in one rh_solve_cases launch (outputs: zeta,
@@ -957,10 +985,12 @@ class Model:
         (rh_array_solve_stats_ext).  Added keys: mean_offsets [n,6N], statics_iters, statics_status,
         and the reference's array_mooring channels (raft/raft_model.py:351-373) Tmoor_avg [n,2L],
         Tmoor_std, Tmoor_PSD [n,2L,nw] (over w[0]), Tmoor_max / Tmoor_min (+- 3 std).  One sea state
-        per case; potSecOrder > 0 and a K_array / C_moor fixture raise NotImplementedError."""
+        per case; potSecOrder > 0 and a K_array / C_moor fixture raise NotImplementedError.
+        rotor_device=True (with statics=True, the form that evaluates the rotors) takes every FOWT's
+        blade-element loads from one device launch per FOWT, as analyzeCasesBatch does."""
         import torch
         if statics:
-            return self._analyze_array_statics(cases, tol, host, pose_chunk)
+            return self._analyze_array_statics(cases, tol, host, pose_chunk, rotor_device)
         P = prepared if prepared is not None else self.prepareArrayBatch(cases)
         nf, n, nw = self.nFOWT, P["n"], self.nw
         dds, cs, prep, dev = P["dds"], P["cs"], P["prep"], P["dev"]
@@ -999,7 +1029,7 @@ class Model:
             return {k: v.cpu().numpy() for k, v in out.items() if k != "_keep"}
         return out
 
-    def _analyze_array_statics(self, cases, tol, host, pose_chunk):
+    def _analyze_array_statics(self, cases, tol, host, pose_chunk, rotor_device=False):
         """analyzeArrayBatch(statics=True): see there.  Every FOWT is moved to its pose as solveStatics
         leaves it (turbine and hydro constants at the reference pose, members and rotors at the
         offset pose, its own system's C_moor from the device)."""
@@ -1017,7 +1047,8 @@ class Model:
         if any(len(s[0]) > 1 for s in seas):
             raise NotImplementedError("analyzeArrayBatch(statics=True): several sea states per case")
         self._calc_bem_once()
-        sb = self.solveStaticsArrayBatch(cases, host=False)
+        sb = self.solveStaticsArrayBatch(cases, host=False, rotor_device=rotor_device)
+        bems = self._array_rotor_loads(cases) if rotor_device else None   # (every FOWT at its reference pose)
         nf, n, nw = self.nFOWT, len(cases), self.nw
         Xs = sb["X"].cpu().numpy()
         Cm = [None if c is None else c.cpu().numpy() for c in sb["C_moor"]]
@@ -1035,7 +1066,7 @@ class Model:
                     if isinstance(ci.get("wind_speed"), list):
                         ci["wind_speed"] = ci["wind_speed"][f]
                     fowt.setPosition(X_ref[f])
-                    fowt.calcTurbineConstants(ci, ptfm_pitch=0)
+                    fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[f][i] if bems else None)
                     fowt.calcHydroConstants()
                     fowt.setPosition(Xs[i, 6 * f:6 * f + 6])
                     if Cm[f] is not None:

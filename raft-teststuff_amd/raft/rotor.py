@@ -279,8 +279,27 @@ class Rotor(RNA):
         self.Ng = turbine["gear_ratio"]
 
     # ------------------------------------------------------------------ aerodynamics
-    def runCCBlade(self, U0, tilt=0, yaw_misalign=0):
-        """One CCBlade evaluation at the scheduled operating point (raft/raft_rotor.py:699-768)."""
+    def operating_point(self, U0):
+        """The scheduled operating point (Uhub, Omega_rpm, pitch_deg) at wind speed U0, as
+        runCCBlade forms it."""
+        Uhub = U0 * self.speed_gain
+        return Uhub, np.interp(Uhub, self.Uhub, self.Omega_rpm), np.interp(Uhub, self.Uhub, self.pitch_deg)
+
+    def inflow_angles(self, case):
+        """(turbine_tilt, yaw_misalign) [rad] of a case at the rotor's current pose, as calcAero
+        forms them (it sets the inflow and turbine headings and calls setYaw, and so does this)."""
+        heading = get_from_dict(case, "wind_heading", shape=0, default=0.0)
+        self.inflow_heading = np.radians(heading)
+        self.turbine_heading = np.radians(get_from_dict(case, "turbine_heading", shape=0, default=0.0))
+        self.setYaw()
+        yaw_misalign = np.arctan2(self.q[1], self.q[0]) - self.inflow_heading
+        turbine_tilt = np.arctan2(self.q[2], np.hypot(self.q[0], self.q[1]))
+        return turbine_tilt, yaw_misalign
+
+    def runCCBlade(self, U0, tilt=0, yaw_misalign=0, bem=None):
+        """One CCBlade evaluation at the scheduled operating point (raft/raft_rotor.py:699-768).
+        bem: a (loads, derivs) pair in the form of CCBlade.evaluate that stands in for the
+        evaluation (the batched device solve, FOWT.rotorLoadsBatch)."""
         if self.ccblade is None:
             raise NotImplementedError("rotor aerodynamics need CCBlade (a dependency of the reference, "
                                       "raft/raft_rotor.py:17-20), which is not installed; attach a CCBlade-compatible "
@@ -290,7 +309,10 @@ class Rotor(RNA):
         pitch_deg = np.interp(Uhub, self.Uhub, self.pitch_deg)
         self.ccblade.tilt = tilt
         self.ccblade.yaw = yaw_misalign
-        loads, derivs = self.ccblade.evaluate(Uhub, Omega_rpm, pitch_deg, coefficients=True)
+        if bem is not None:
+            loads, derivs = bem
+        else:
+            loads, derivs = self.ccblade.evaluate(Uhub, Omega_rpm, pitch_deg, coefficients=True)
         self.U_case, self.Omega_case, self.pitch_case = Uhub, Omega_rpm, pitch_deg
         self.aero_torque, self.aero_power, self.aero_thrust = loads["Q"][0], loads["P"][0], loads["T"][0]
         J = {("P", "r"): derivs["dP"]["dr"]}
@@ -302,11 +324,11 @@ class Rotor(RNA):
         self.J = J
         return loads, derivs
 
-    def calcAero(self, case, current=False, display=0):
+    def calcAero(self, case, current=False, display=0, bem=None):
         """Mean hub loads f0 [6], wind excitation f [6, nw], aero-servo added mass a and damping
         b [6, 6, nw] about the hub in global orientation (raft/raft_rotor.py:788-1005):
         aeroServoMod 1 = thrust-speed derivative only; 2 = with the pitch / torque PI control
-        loop closed through the drivetrain."""
+        loop closed through the drivetrain.  bem: see runCCBlade."""
         if current:
             raise NotImplementedError("underwater rotors (current-driven) are outside the accelerated path")
         self.a = np.zeros([6, 6, self.nw])
@@ -320,7 +342,7 @@ class Rotor(RNA):
         self.setYaw()
         yaw_misalign = np.arctan2(self.q[1], self.q[0]) - self.inflow_heading
         turbine_tilt = np.arctan2(self.q[2], np.hypot(self.q[0], self.q[1]))
-        loads, derivs = self.runCCBlade(speed, tilt=turbine_tilt, yaw_misalign=yaw_misalign)
+        loads, derivs = self.runCCBlade(speed, tilt=turbine_tilt, yaw_misalign=yaw_misalign, bem=bem)
         dT_dU = np.atleast_1d(np.diag(derivs["dT"]["dUinf"]))
         dT_dOm = np.atleast_1d(np.diag(derivs["dT"]["dOmega"])) / RPM2RADPS
         dT_dPi = np.atleast_1d(np.diag(derivs["dT"]["dpitch"])) * RAD2DEG

@@ -1,0 +1,204 @@
+"""Rotor blade-element momentum loads on the device (csrc/rh_rotor.h, rh_rotor.hip).
+
+flatten_rotor() turns a raft.ccblade.CCBlade into the tables of rh_rotor; DeviceRotor wraps
+rh_rotor_loads on torch tensors and returns what CCBlade.evaluate returns.  The device covers the
+restatement class with iterRe = 1 and airfoils of one Reynolds number, within the ABI's limits;
+flatten_rotor() refuses everything else with a NotImplementedError that names the reason, before
+any device call.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+from .ccblade import CCBlade, define_curvature
+
+
+class FlatRotor:
+    """The host tables of one rh_rotor record and the ctypes record over them (host pointers only;
+    DeviceRotor adds the device ones)."""
+
+    def __init__(self, scalars, section, nknot, knots, coef):
+        self.scalars = scalars
+        self.section = np.ascontiguousarray(section, dtype=np.float64)
+        self.nknot = np.ascontiguousarray(nknot, dtype=np.int32)
+        self.knots = np.ascontiguousarray(knots, dtype=np.float64)
+        self.coef = np.ascontiguousarray(coef, dtype=np.float64)
+        self.nr, self.nsector = scalars["nr"], scalars["nsector"]
+
+    def fill(self, rec, device_tables=None):
+        for k, v in self.scalars.items():
+            setattr(rec, k, v)
+        rec.pad_ = 0
+        rec.section_host, rec.nknot_host = self.section.ctypes.data, self.nknot.ctypes.data
+        rec.knots_host, rec.coef_host = self.knots.ctypes.data, self.coef.ctypes.data
+        if device_tables is not None:
+            rec.section, rec.nknot, rec.knots, rec.coef = (t.data_ptr() for t in device_tables)
+        return rec
+
+    def record(self):
+        return self.fill(N.RhRotor())
+
+
+def flatten_rotor(ccblade):
+    """The rh_rotor tables of a raft.ccblade.CCBlade.  Host only: no device is touched."""
+    if not isinstance(ccblade, CCBlade):
+        raise NotImplementedError(f"device rotor: rotor.ccblade is a {type(ccblade).__module__}.{type(ccblade).__name__}, "
+                                  "not the restatement class raft.ccblade.CCBlade (another CCBlade evaluates on the host)")
+    if ccblade.iterRe != 1:
+        raise NotImplementedError(f"device rotor: iterRe = {ccblade.iterRe} (only one pass of the Reynolds-number "
+                                  "iteration, iterRe = 1)")
+    nr, nsec = len(ccblade.r), int(ccblade.nSector)
+    if nr < 1 or nr > N.ROTOR_MAX_SECTIONS:
+        raise NotImplementedError(f"device rotor: {nr} blade sections (1 to {N.ROTOR_MAX_SECTIONS})")
+    if nsec < 1 or nsec > N.ROTOR_MAX_SECTORS:
+        raise NotImplementedError(f"device rotor: {nsec} azimuthal sectors (1 to {N.ROTOR_MAX_SECTORS})")
+    splines = []
+    for i, af in enumerate(ccblade.af):
+        if not getattr(af, "one_Re", False):
+            raise NotImplementedError(f"device rotor: airfoil {i} has more than one Reynolds number")
+        for sp in (af.cl_spline, af.cd_spline):
+            tx, ty, c = sp.tck
+            kx, ky = sp.degrees
+            if ky != 1 or len(ty) != 4:
+                raise NotImplementedError(f"device rotor: airfoil {i} has more than one Reynolds number (spline of "
+                                          f"degree {ky} with {len(ty)} knots in Re)")
+            if len(tx) > N.ROTOR_MAX_KNOTS:
+                raise NotImplementedError(f"device rotor: airfoil {i}: {len(tx)} spline knots in alpha (at most "
+                                          f"{N.ROTOR_MAX_KNOTS})")
+            splines.append((i, np.asarray(tx, dtype=float), np.asarray(ty, dtype=float), np.asarray(c, dtype=float), kx))
+    degrees = {s[4] for s in splines}
+    if len(degrees) != 1 or not 1 <= min(degrees) <= 3:
+        raise NotImplementedError(f"device rotor: polar splines of degrees {sorted(degrees)} in alpha (one degree "
+                                  "from 1 to 3 for all airfoils)")
+    kx = degrees.pop()
+    stride = max(len(s[1]) for s in splines)
+    nknot = np.zeros([2, nr], dtype=np.int32)
+    knots = np.zeros([2, nr, stride + 4])
+    coef = np.zeros([2, nr, stride, 2])
+    for n, (i, tx, ty, c, _) in enumerate(splines):
+        p = n % 2                                    # 0 = cl, 1 = cd
+        nknot[p, i] = len(tx)
+        knots[p, i, :len(tx)] = tx
+        knots[p, i, len(tx):stride] = tx[-1]
+        knots[p, i, stride:] = ty
+        coef[p, i, :len(tx) - kx - 1] = c.reshape(len(tx) - kx - 1, 2)
+    # the stations' geometry: the inflow's (define_curvature of the stations) and thrust_torque's
+    # (the path hub, stations, tip, where the loads are zero)
+    x_az, y_az, z_az, cone, _ = define_curvature(ccblade.r, ccblade.precurve, ccblade.presweep, ccblade.precone)
+    rfull = np.r_[ccblade.Rhub, ccblade.r, ccblade.Rtip]
+    curvefull = np.r_[0.0, ccblade.precurve, ccblade.precurveTip]
+    sweepfull = np.r_[0.0, ccblade.presweep, ccblade.presweepTip]
+    _, _, z_full, cone_full, s = define_curvature(rfull, curvefull, sweepfull, ccblade.precone)
+    ds = s[1:] - s[:-1]
+    section = np.zeros([N.RS_COUNT, nr])
+    section[N.RS["R"]], section[N.RS["CHORD"]], section[N.RS["THETA"]] = ccblade.r, ccblade.chord, ccblade.theta
+    section[N.RS["XAZ"]], section[N.RS["YAZ"]], section[N.RS["ZAZ"]] = x_az, y_az, z_full[1:-1]
+    section[N.RS["CONE"]] = cone
+    section[N.RS["WEIGHT"]] = 0.5 * (ds[:-1] + ds[1:])
+    section[N.RS["CONE_PATH"]] = cone_full[1:-1]
+    opt = ccblade.bemoptions
+    scalars = dict(nr=nr, nsector=nsec, B=int(ccblade.B), usecd=int(bool(opt["usecd"])),
+                   tiploss=int(bool(opt["tiploss"])), hubloss=int(bool(opt["hubloss"])),
+                   wakerotation=int(bool(opt["wakerotation"])), kx=int(kx), knot_stride=int(stride),
+                   Rhub=float(ccblade.Rhub), Rtip=float(ccblade.Rtip), rho=float(ccblade.rho), mu=float(ccblade.mu),
+                   precone=float(ccblade.precone), hubHt=float(ccblade.hubHt), shearExp=float(ccblade.shearExp))
+    return FlatRotor(scalars, section, nknot, knots, coef)
+
+
+def bem_pair(nr, loads8, dloads6, Omega_rpm):
+    """One operating point's (loads, derivs) in the form of CCBlade.evaluate (npts = 1): what
+    Rotor.runCCBlade takes as `bem`."""
+    T, Y, Z, Q, My, Mz, Mb, P = (np.array([v], dtype=float) for v in loads8)
+    loads = dict(T=T, Y=Y, Z=Z, Q=Q, My=My, Mz=Mz, Mb=Mb, P=P)
+    derivs = {}
+    if dloads6 is not None:
+        d = np.asarray(dloads6, dtype=float).reshape(2, 3)
+        w = Omega_rpm * np.pi / 30.0
+
+        def block(v):
+            return {"dUinf": np.diag(v[0:1]), "dOmega": np.diag(v[1:2]), "dpitch": np.diag(v[2:3]),
+                    "dr": np.zeros((1, nr))}
+        derivs["dT"] = block(d[0])
+        derivs["dQ"] = block(d[1])
+        derivs["dP"] = block(d[1] * w + np.array([0.0, Q[0] * np.pi / 30.0, 0.0]))
+    return loads, derivs
+
+
+class DeviceRotor:
+    """One or more rotors resident on the device; operating points pick a rotor through rot_idx."""
+
+    def __init__(self, rotors, device=0):
+        self.flat = [r if isinstance(r, FlatRotor) else flatten_rotor(r) for r in rotors]   # refusals first
+        import torch
+        self.torch = torch
+        self.dev_index = device
+        self.device = torch.device(f"cuda:{device}")
+        self.nrot = len(self.flat)
+        self.nr_max = max(f.nr for f in self.flat)
+        self.ns_max = max(f.nsector for f in self.flat)
+        self._tables = []
+        self._arr = (N.RhRotor * self.nrot)()
+        for i, f in enumerate(self.flat):
+            tabs = (torch.tensor(f.section, dtype=torch.float64, device=self.device).contiguous(),
+                    torch.tensor(f.nknot, dtype=torch.int32, device=self.device).contiguous(),
+                    torch.tensor(f.knots, dtype=torch.float64, device=self.device).contiguous(),
+                    torch.tensor(f.coef, dtype=torch.float64, device=self.device).contiguous())
+            self._tables.append(tabs)
+            f.fill(self._arr[i], tabs)
+        raw = np.frombuffer(bytes(self._arr), dtype=np.uint8).copy()
+        self._arr_dev = torch.tensor(raw, dtype=torch.uint8, device=self.device)
+
+    def launch(self, rot_idx, op, derivatives=True, sections=False):
+        """rh_rotor_loads at op [n, 5] = Uinf, Omega_rpm, pitch_deg, tilt, yaw.  rot_idx [n] (any
+        integers: an index outside [0, nrot) gives that row status 3) or None.  Returns device
+        tensors loads [n,8], dloads [n,2,3] or None, sec [n,ns_max,nr_max,3] or None, status [n]."""
+        torch = self.torch
+        op = torch.as_tensor(np.asarray(op, dtype=float) if not torch.is_tensor(op) else op, dtype=torch.float64,
+                             device=self.device).contiguous()
+        n = op.shape[0]
+        if list(op.shape) != [n, 5]:
+            raise ValueError(f"expected op of shape [n, 5], got {list(op.shape)}")
+        idx = None
+        if rot_idx is not None:
+            idx = np.asarray(rot_idx, dtype=np.int32)
+            if idx.shape != (n,):
+                raise ValueError(f"rot_idx: {n} entries expected")
+            idx = torch.tensor(idx, dtype=torch.int32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        loads = torch.empty([n, 8], **f64)
+        dloads = torch.empty([n, 2, 3], **f64) if derivatives else None
+        sec = torch.empty([n, self.ns_max, self.nr_max, 3], **f64) if sections else None
+        status = torch.empty([n], dtype=torch.int32, device=self.device)
+        N.check(N.lib().rh_rotor_loads(N.context(self.dev_index), self._arr, N.ptr(self._arr_dev), self.nrot, n,
+                                       N.ptr(idx), N.ptr(op), N.ptr(loads), N.ptr(dloads), N.ptr(sec), N.ptr(status),
+                                       N.stream_handle(torch, self.device)), "rh_rotor_loads")
+        return dict(loads=loads, dloads=dloads, sec=sec, status=status, _keep=(op, idx))
+
+    def evaluate(self, rot_idx, Uinf, Omega_rpm, pitch_deg, tilt, yaw, derivatives=True, sections=False):
+        """CCBlade.evaluate of every operating point (tilt and yaw [rad] as Rotor.runCCBlade sets
+        them on the CCBlade object).  Returns (loads, derivs, status) and, with sections, sec: loads
+        a dict of arrays [n] (T, Y, Z, Q, My, Mz, Mb, P), derivs the dict of dT / dQ / dP blocks with
+        their diagonal matrices (empty without derivatives), status [n], sec [n,ns_max,nr_max,3]."""
+        cols = np.broadcast_arrays(*(np.atleast_1d(np.asarray(v, dtype=float)) for v in
+                                     (Uinf, Omega_rpm, pitch_deg, tilt, yaw)))
+        op = np.stack(cols, axis=1)
+        out = self.launch(rot_idx, op, derivatives, sections)
+        L = out["loads"].cpu().numpy()
+        status = out["status"].cpu().numpy()
+        loads = {k: L[:, i].copy() for i, k in enumerate(("T", "Y", "Z", "Q", "My", "Mz", "Mb", "P"))}
+        derivs = {}
+        if derivatives:
+            d = out["dloads"].cpu().numpy()
+            w = op[:, 1] * np.pi / 30.0
+            n = len(op)
+
+            def block(v):
+                return {"dUinf": np.diag(v[:, 0]), "dOmega": np.diag(v[:, 1]), "dpitch": np.diag(v[:, 2]),
+                        "dr": np.zeros((n, self.nr_max))}
+            derivs["dT"] = block(d[:, 0])
+            derivs["dQ"] = block(d[:, 1])
+            derivs["dP"] = block(d[:, 1] * w[:, None] + np.c_[0 * w, loads["Q"] * np.pi / 30.0, 0 * w])
+        if sections:
+            return loads, derivs, status, out["sec"].cpu().numpy()
+        return loads, derivs, status

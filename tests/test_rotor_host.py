@@ -1,0 +1,290 @@
+"""CPU check of the device rotor restatement (raft-teststuff_amd/csrc/rh_rotor.h) against the Python
+it restates (raft/ccblade.py): the header is compiled for the host with g++ (tools/rotor_host.cpp),
+so the same spline, section, root-find, derivative and sector code the GPU runs is compared here
+operation for operation, without a GPU.  Also the `bem=` refactor of Rotor.calcAero, the refusals
+of raft/rotor_device.py and the new ABI symbol."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, load_design
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import rotor_cases as RC  # noqa: E402
+
+TILT, YAW = 0.1, 0.05   # [rad]: a tilted, yawed inflow, so that the four sectors differ
+
+# The worst relative difference of the section functions (residual, a, ap, Np, Tp, alpha, W, Re)
+# between the host-compiled header and the Python over the cases of test_section_functions,
+# measured on the CPU: 1.66e-16 of the value itself (under one unit in the last place: the two run
+# the same operations in the same order).  The test asserts at ten times that, and never above 1e-10.
+SECTION_MEASURED = 1.66e-16
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return RC.host_lib()
+
+
+@pytest.fixture(scope="module")
+def volturn():
+    from raft.rotor_device import flatten_rotor
+    cc, rot, model = RC.volturn_ccblade()
+    return cc, rot, flatten_rotor(cc)
+
+
+def schedule_points(rot):
+    return [(U, float(np.interp(U, rot.Uhub, rot.Omega_rpm)), float(np.interp(U, rot.Uhub, rot.pitch_deg)))
+            for U in RC.SCHEDULE_U]
+
+
+# ------------------------------------------------------------------------------ splines
+def test_splines_match_bispev(lib, volturn):
+    """Every section's cl and cd spline at 200 alphas across the knot range, at both ends, outside
+    them (clamped) and at Re = 1e1, 1e6, 1e15, to 1e-12 of the largest coefficient."""
+    cc, _, flat = volturn
+    kx, stride = flat.scalars["kx"], flat.scalars["knot_stride"]
+    counts = set()
+    for i, af in enumerate(cc.af):
+        for p, sp in enumerate((af.cl_spline, af.cd_spline)):
+            tx, ty, c = sp.tck
+            assert sp.degrees == (kx, 1) and len(ty) == 4
+            counts.add(len(tx))
+            lo, hi = tx[0], tx[-1]
+            alpha = np.r_[np.linspace(lo, hi, 200), lo, hi, lo - 0.5, hi + 0.5, np.nextafter(hi, lo), tx[kx + 1:-kx - 1]]
+            for Re in (1e1, 1e6, 1e15, 1e0, 1e16):
+                y = np.full_like(alpha, Re)
+                out = np.zeros_like(alpha)
+                # from the record's padded tables, as the device reads them
+                lib.rh_rotor_spline_host(int(flat.nknot[p, i]), kx, flat.knots[p, i].ctypes.data,
+                                         flat.knots[p, i, stride:].ctypes.data, flat.coef[p, i].ctypes.data,
+                                         len(alpha), alpha.ctypes.data, y.ctypes.data, out.ctypes.data)
+                ref = sp.ev(alpha, y)
+                err = np.abs(out - ref).max()
+                assert err <= 1e-12 * np.abs(c).max(), (i, p, Re, err)
+    assert len(counts) > 3      # smoothing gave the sections different knot counts
+
+
+# ------------------------------------------------------------------------------ section functions
+def _rel(got, ref):
+    got, ref = np.asarray(got, dtype=float), np.asarray(ref, dtype=float)
+    zero = ref == 0
+    assert np.all(got[zero] == 0), (got, ref)
+    return float(np.max(np.abs(got[~zero] - ref[~zero]) / np.abs(ref[~zero]), initial=0.0))
+
+
+def test_section_functions(lib, volturn):
+    """Residual, a, ap (induction_factors), alpha, W, Re (relative_wind) and the whole section at a
+    given phi (_run_bem, _loads) against the Python in every region."""
+    import raft.ccblade as C
+    cc, _, flat = volturn
+    B, Rhub, Rtip = cc.B, cc.Rhub, cc.Rtip
+    r, chord, Vx, Vy = 0.9 * Rtip, 3.0, 9.0, 60.0
+    hit = set()
+    worst = 0.0
+
+    def induction(phi, cl, cd, flags=15, r=r, Vx=Vx, Vy=Vy):
+        nonlocal worst
+        opts = dict(usecd=bool(flags & 1), hubloss=bool(flags & 2), tiploss=bool(flags & 4), wakerotation=bool(flags & 8))
+        with np.errstate(all="ignore"):
+            ref = C.induction_factors(r, chord, Rhub, Rtip, np.float64(phi), cl, cd, B, Vx, Vy, **opts)
+        out = np.zeros(3)
+        lib.rh_rotor_induction_host(r, chord, Rhub, Rtip, phi, cl, cd, B, Vx, Vy, flags, out.ctypes.data)
+        worst = max(worst, _rel(out, ref))
+        return ref
+
+    for flags in (15, 14, 13, 11, 7, 0):
+        f, a, ap = induction(0.2, 0.8, 0.01, flags)                  # momentum region
+        assert 0 < a < 0.4
+        hit.add("momentum")
+        f, a, ap = induction(0.03, 1.2, 0.012, flags)                # Buhl's correction
+        hit.add("buhl")
+        f, a, ap = induction(-0.05, 1.5, 0.01, flags)                # phi < 0, k > 1
+        assert a > 1
+        hit.add("brake k > 1")
+        f, a, ap = induction(-0.6, 0.5, 0.01, flags)                 # phi < 0, k <= 1
+        assert a == 0.0
+        hit.add("brake k <= 1")
+    # |g3| < 1e-6: with the tip loss F < 5/6, k = (25/9 - 2 F) / (2 F) > 2/3 puts g3 at rounding
+    phi, rt = 0.12, 0.97 * Rtip
+    sphi, cphi = np.sin(phi), np.cos(phi)
+    F = 2.0 / np.pi * np.arccos(np.exp(-(B / 2.0 * (Rtip - rt) / (rt * abs(sphi)))))
+    assert F < 5.0 / 6
+    k = (25.0 / 9 - 2 * F) / (2 * F)
+    sigma_t = B / 2.0 / np.pi * chord / rt
+    cl = k * 4.0 * F * sphi * sphi / (sigma_t * cphi)
+    kk = sigma_t * (cl * cphi) / 4.0 / F / sphi / sphi
+    assert kk > 2.0 / 3 and abs(2.0 * F * kk - (25.0 / 9 - 2 * F)) < 1e-6
+    f, a, ap = induction(phi, cl, 0.0, flags=4 | 8, r=rt)            # tip loss only, no drag in cn
+    assert a == 1.0 - 1.0 / 2.0 / np.sqrt(2.0 * F * kk - (4.0 / 3 - F) * F)
+    hit.add("g3")
+
+    def relwind(phi, a, ap):
+        nonlocal worst
+        ref = C.relative_wind(phi, a, ap, Vx, Vy, 0.02, chord, 0.05, cc.rho, cc.mu)
+        out = np.zeros(3)
+        lib.rh_rotor_relative_wind_host(phi, a, ap, Vx, Vy, 0.02, chord, 0.05, cc.rho, cc.mu, out.ctypes.data)
+        worst = max(worst, _rel(out, ref))
+    relwind(0.3, 0.2, 0.05)
+    relwind(0.3, 11.0, 0.05)
+    hit.add("|a| > 10")
+    relwind(-0.3, -0.2, -12.0)
+    hit.add("|ap| > 10")
+    relwind(-0.3, 21.0, 0.1)     # a = k / (k - 1) at k = 1.05
+
+    # the whole section at phi: _run_bem and _loads with the section's own splines
+    rec = flat.record()
+    cc.pitch = 0.03
+    out = np.zeros(9)
+    for i in (0, 5, 12, 19):
+        args = (cc.r[i], cc.chord[i], cc.theta[i], cc.af[i], 7.5, 8.0 * cc.r[i] / 10)
+        for phi in (1e-6, 0.02, 0.15, 0.9, np.pi / 2, 2.4, np.pi - 1e-6, -1e-6, -0.04, -np.pi / 4):
+            with np.errstate(all="ignore"):
+                fz = cc._errf(np.float64(phi), *args)
+                Np, Tp, a, ap, alpha, clv, cdv, W = cc._loads(np.float64(phi), True, *args)
+            lib.rh_rotor_section_eval_host(ctypes.addressof(rec), i, phi, 1, args[4], args[5], cc.pitch, out.ctypes.data)
+            worst = max(worst, _rel(out, [fz, a, ap, Np, Tp, alpha, clv, cdv, W]))
+    assert hit == {"momentum", "buhl", "brake k > 1", "brake k <= 1", "g3", "|a| > 10", "|ap| > 10"}
+    print(f"section functions: worst relative difference {worst:.3e}")
+    assert worst <= min(10 * SECTION_MEASURED, 1e-10), worst
+
+
+# ------------------------------------------------------------------------------ root, loads, derivatives
+@pytest.fixture(scope="module")
+def reference(volturn):
+    cc, rot, _ = volturn
+    pts = RC.POINTS + schedule_points(rot)
+    return pts, RC.python_reference(cc, pts, TILT, YAW, derivs_at=range(len(RC.POINTS), len(pts)))
+
+
+def test_root_loads_and_derivatives(lib, volturn, reference):
+    """phi to 1e-11 at every section and sector of the ten operating points, forces to 1e-9 |T|,
+    moments to 1e-9 |Q|, and the six derivatives at the five schedule points to their self-calibrated
+    bars (helpers/rotor_cases.py)."""
+    cc, rot, flat = volturn
+    pts, ref = reference
+    op = np.array([[U, Om, pit, TILT, YAW] for U, Om, pit in pts], dtype=float)
+    loads, dl, sec, status = RC.host_loads(lib, flat, op)
+    RC.check_parity(ref, loads, sec, dl, status, "host header")
+    assert np.all(np.isfinite(loads))
+    # dloads = NULL: the same loads, bit for bit
+    loads2, _, sec2, status2 = RC.host_loads(lib, flat, op, derivatives=False)
+    assert np.array_equal(loads, loads2) and np.array_equal(sec, sec2)
+    # the brackets the points are there for
+    rec = flat.record()
+    out = np.zeros(11)
+    brackets = np.zeros([len(RC.POINTS), flat.nsector, flat.nr], dtype=int)
+    for p in range(len(RC.POINTS)):
+        for j in range(flat.nsector):
+            for i in range(flat.nr):
+                lib.rh_rotor_section_solve_host(ctypes.addressof(rec), i, op[p].ctypes.data,
+                                                np.radians(360.0 * j / flat.nsector), 0, out.ctypes.data)
+                brackets[p, j, i] = int(out[10])
+    assert np.all(brackets[0] == 1)
+    assert np.sum(brackets[3] == 3) >= 1 and np.sum(brackets[4] == 3) >= 1   # (1 and 4 sections at this tilt and yaw)
+    assert np.all(brackets[9] == 0)                                  # not rotating
+    assert ref["loads"][1, 3] < 0 and ref["loads"][2, 3] < 0         # negative torque
+    assert np.all(ref["loads"][5:8, 0] < 0)                          # negative thrust
+
+
+def test_second_bracket_points(lib, volturn):
+    """The search on the CPU for points that reach the second bracket [-pi/4, -1e-6): a feathered,
+    slowly turning rotor (15 m/s, 0.5 rpm, 90 deg: two sections) is a physical one, and a rotor
+    turning backwards (8 m/s, -5 rpm, 0 deg) puts more than half of its sections there.  Both against
+    the Python with the bars of the ten points.  The same search (wind -25 to 40 m/s, -7.5 to 12 rpm,
+    pitch -20 to 90 deg, this tilt and yaw) found no section without a sign change in all three
+    brackets, so status 1 has no Python case to be compared with."""
+    cc, rot, flat = volturn
+    pts = RC.SECOND_BRACKET_POINTS
+    ref = RC.python_reference(cc, pts, TILT, YAW)
+    op = np.array([[U, Om, pit, TILT, YAW] for U, Om, pit in pts], dtype=float)
+    loads, dl, sec, status = RC.host_loads(lib, flat, op)
+    RC.check_parity(ref, loads, sec, dl, status, "host header")
+    rec = flat.record()
+    out = np.zeros(11)
+    for p, least in ((0, 2), (1, flat.nsector * flat.nr // 2)):
+        n2 = 0
+        for j in range(flat.nsector):
+            for i in range(flat.nr):
+                lib.rh_rotor_section_solve_host(ctypes.addressof(rec), i, op[p].ctypes.data,
+                                                np.radians(360.0 * j / flat.nsector), 0, out.ctypes.data)
+                n2 += int(out[10]) == 2
+        assert n2 >= least, (pts[p], n2)
+        assert np.sum(ref["sec"][p, :, :, 0] < 0) == n2      # ... and the Python's phi is negative exactly there
+
+
+# ------------------------------------------------------------------------------ bem= is a pure refactor
+@pytest.mark.parametrize("mod", [1, 2])
+def test_bem_argument_is_a_pure_refactor(mod):
+    """calcAero(case, bem=cc.evaluate(...)) equals calcAero(case) bit for bit in f0, f, a and b."""
+    import raft
+    d = load_design("VolturnUS-S_aero")
+    d["turbine"]["aeroServoMod"] = mod
+    rot = raft.Model(d).fowtList[0].rnaList[0]
+    assert rot.aeroServoMod == mod
+    case = {"wind_speed": 9.0, "wind_heading": 20.0, "turbulence": 0.1, "turbine_status": "operating", "yaw_misalign": 0}
+    f0, f, a, b = (np.array(x) for x in rot.calcAero(dict(case)))
+    tilt, yaw = rot.inflow_angles(case)
+    rot.ccblade.tilt, rot.ccblade.yaw = tilt, yaw
+    bem = rot.ccblade.evaluate(*rot.operating_point(9.0), coefficients=True)
+    calls = []
+    real = rot.ccblade.evaluate
+    rot.ccblade.evaluate = lambda *a_, **k_: calls.append(1) or real(*a_, **k_)
+    g0, g, ga, gb = rot.calcAero(dict(case), bem=bem)
+    assert not calls                                              # the pair stood in for the evaluation
+    assert np.array_equal(f0, g0) and np.array_equal(f, g) and np.array_equal(a, ga) and np.array_equal(b, gb)
+    assert np.any(f0) and np.any(b)
+
+
+# ------------------------------------------------------------------------------ refusals
+def test_unsupported_rotors_are_refused(monkeypatch, volturn):
+    """Each unsupported kind raises NotImplementedError, naming its condition, before any device call."""
+    from raft import _native as N
+    from raft.rotor_device import DeviceRotor, flatten_rotor
+    cc, _, _ = volturn
+
+    def no_device(*a, **k):
+        raise AssertionError("device touched before the refusal")
+    monkeypatch.setattr(N, "lib", no_device)
+    monkeypatch.setattr(N, "context", no_device)
+    sys.path.insert(0, GOLDEN)
+    from fake_ccblade import FakeCCBlade
+    fake = FakeCCBlade.__new__(FakeCCBlade)
+    with pytest.raises(NotImplementedError, match="not the restatement class"):
+        DeviceRotor([fake])
+    two = RC.resampled(cc, 20, 4)
+    two.iterRe = 2
+    with pytest.raises(NotImplementedError, match="iterRe = 2"):
+        DeviceRotor([two])
+    with pytest.raises(NotImplementedError, match="65 blade sections"):
+        DeviceRotor([RC.resampled(cc, 65, 4)])
+    with pytest.raises(NotImplementedError, match="17 azimuthal sectors"):
+        DeviceRotor([RC.resampled(cc, 20, 17)])
+    from raft.ccblade import CCAirfoil
+    alpha = np.linspace(-180, 180, 73)
+    multi = CCAirfoil(alpha, [1e5, 1e6, 1e7], np.outer(np.sin(np.radians(alpha)), [1, 1.1, 1.2]),
+                      np.outer(1 - np.cos(np.radians(alpha)), [1, 1, 1]) + 0.01)
+    many = RC.resampled(cc, 20, 4)
+    many.af = [multi] * 20
+    with pytest.raises(NotImplementedError, match="more than one Reynolds number"):
+        flatten_rotor(many)
+
+
+# ------------------------------------------------------------------------------ ABI
+def test_abi_exports_rotor_loads():
+    import __graft_entry__ as g
+    g.build()
+    from raft import _native as N
+    out = subprocess.run(["nm", "-D", "--defined-only", g.LIB], capture_output=True, text=True, check=True).stdout
+    assert " T rh_rotor_loads\n" in out
+    L = N.lib()
+    assert L.rh_version() == 7
+    null = [None] * 7
+    assert L.rh_rotor_loads(None, None, None, 1, 1, *null) == N.RH_EINVAL
+    assert b"null context" in L.rh_last_error()
+    assert ctypes.sizeof(N.RhRotor) == 10 * 4 + 7 * 8 + 8 * 8
+    assert (N.ROTOR_MAX_SECTIONS, N.ROTOR_MAX_SECTORS, N.ROTOR_MAX_KNOTS) == (64, 16, 128)
