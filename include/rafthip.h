@@ -467,7 +467,9 @@ int rh_heading_response(rh_ctx* ctx, const rh_design* designs, int ndesign, int 
  * Bmat (0 = the largest nn of the designs passed; RH_EINVAL when smaller than that), so a call
  * over a subset of the designs of the rh_solve_cases call that wrote Bmat reads it correctly.
  * fext: [ncase][6][nw] or NULL.  A case whose design or heading index is out of range gets NaN
- * rows (no table is read). */
+ * rows (no table is read).  A bin whose elimination meets an exactly zero pivot (a singular Z; the
+ * reference's solve raises LinAlgError there) gets NaN in its 6 rows, never finite numbers; the
+ * other bins of the case are unaffected.  The same holds for rh_heading_response. */
 int rh_heading_response_ext(rh_ctx* ctx, const rh_design* designs, int ndesign, int ncase,
                             const int* design_idx, const int* head, const double* zeta,
                             const double* B_drag, const double* Bmat, int bmat_nn, const rh_c128* fext,
@@ -531,7 +533,24 @@ int rh_channel_stats(rh_ctx* ctx, int ncase, int nrow, int ndof, int nw, double 
 
 /* Coupled array solve (raft/raft_model.py:1021-1065) for nf FOWTs, 6nf <= 12:
  * Z_sys = blockdiag(Z_i) + K ; Xi = Z_sys^-1 F.  Z: [nf][nw][36] per-FOWT impedances,
- * K: [6nf*6nf] array mooring stiffness (or NULL), F: [6nf][nw], Xi out: [6nf][nw]. */
+ * K: [6nf*6nf] array mooring stiffness (or NULL), F: [6nf][nw], Xi out: [6nf][nw].
+ *
+ * Singular systems and accuracy (this call, rh_system_solve_batch, rh_array_response[_stats] and
+ * rh_array_solve_stats[_ext]):
+ *  - NaN rule.  A (case, bin) whose elimination meets an exactly zero pivot gets NaN in all its
+ *    6 nf rows (the reference raises LinAlgError("Singular matrix") there); the statistics of the
+ *    array calls inherit it (that bin's psd and the case's std are NaN).  Other bins and cases are
+ *    unaffected.  Nothing is reported through the return code.
+ *  - One FOWT is a 6 x 6 elimination with partial pivoting: backward stable like LAPACK's.
+ *  - Two FOWTs are solved by the 6 x 6 blocks of Z_sys = [[A, K12], [K21, D]], A = Z_1 + K_11:
+ *    A is factored first, then the Schur complement D - K21 A^-1 K12.  Pivoting stays inside each
+ *    block, so (a) a singular A gives NaN rows even where Z_sys itself is regular (e.g. A = 0 with
+ *    K12 = K21 = I), a stated deviation from the reference, which solves such a system, and (b) the
+ *    normwise backward error grows with the conditioning of A, not of Z_sys: eta <= 8 u kappa_2(A),
+ *    u = 2^-53 (measured about 0.1 u kappa_2(A), DESIGN.md "Accuracy of the dense solves"; the farm
+ *    golden reaches kappa_2(A) = 1.7e5).  With rh_set_solver(ctx, 1)
+ *    rh_system_solve[_batch] runs a 12 x 12 elimination that pivots across the blocks instead: it has
+ *    neither limitation (it solves A = 0, and is backward stable whatever kappa_2(A)). */
 int rh_system_solve(rh_ctx* ctx, int nf, int nw, const rh_c128* Z, const double* K,
                     const rh_c128* F, rh_c128* Xi, rh_stream stream);
 

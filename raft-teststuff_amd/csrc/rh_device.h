@@ -109,7 +109,8 @@ __device__ __forceinline__ bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
 // A holds L below the diagonal, U above, the reciprocal pivots on it; piv[k] the row exchanged
 // with k at step k.  Rows are exchanged in columns >= k only, so the multipliers of column k
 // stay where they were formed and lu_apply replays each exchange before that column's
-// elimination (as lu_solve does in one pass).  Returns false on an exactly zero pivot.
+// elimination (as lu_solve does in one pass).  Returns false on an exactly zero pivot, after which
+// the factorisation holds NaN and lu_apply returns NaN in every row.
 template <int N>
 __device__ __forceinline__ bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
   bool ok = true;
@@ -136,7 +137,11 @@ __device__ __forceinline__ bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
         }
       }
     }
-    const cd pv = best != 0.0 ? A[k][k] : mk(1.0, 0.0);
+    // an exactly zero pivot is not replaced: 1 / 0 = inf and 0 * inf = NaN, so its reciprocal is NaN, and
+    // with it the multipliers of this column, the trailing block, every later pivot and all N rows of
+    // whatever lu_apply solves with this factorisation (a product with NaN is NaN, also for a zero
+    // factor).  Callers need no flag to keep finite numbers from being stored.
+    const cd pv = A[k][k];
     const double inv = 1.0 / (pv.r * pv.r + pv.i * pv.i);
     const cd rinv = mk(pv.r * inv, -pv.i * inv);
     A[k][k] = rinv;

@@ -598,9 +598,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_heading_resp(HeadArgs a) {
   }
   cd Z[6][6];
   assemble_z(d, mbc, b, d.w[b], bd, Z);
-  lu_solve<6>(Z, F);
+  // an exactly zero pivot (the reference: LinAlgError) leaves NaN in this bin's rows, never finite numbers
+  const bool ok = lu_solve<6>(Z, F);
+  const cd bad = mk(__builtin_nan(""), __builtin_nan(""));
 #pragma unroll
-  for (int c = 0; c < 6; ++c) st(a.Xi + ((size_t)ic * 6 + c) * nw + b, F[c]);
+  for (int c = 0; c < 6; ++c) st(a.Xi + ((size_t)ic * 6 + c) * nw + b, ok ? F[c] : bad);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -900,6 +902,7 @@ __global__ __launch_bounds__(kSysThreads) void k_system_solve(int N, int nw, con
         Ar(6 * f + i, 6 * f + j) = z.r + kr;
         Ai(6 * f + i, 6 * f + j) = z.i;
       }
+  bool ok = true;          // false after an exactly zero pivot: the bin's rows become NaN
   for (int k = 0; k < N; ++k) {
     int p = k;
     double best = fabs(Ar(k, k)) + fabs(Ai(k, k));
@@ -907,6 +910,7 @@ __global__ __launch_bounds__(kSysThreads) void k_system_solve(int N, int nw, con
       const double v = fabs(Ar(i, k)) + fabs(Ai(i, k));
       if (v > best) { best = v; p = i; }
     }
+    ok = ok && (best != 0.0);
     if (p != k) {
       for (int j = k; j < N; ++j) {
         double tr = Ar(k, j), ti = Ai(k, j);
@@ -933,7 +937,7 @@ __global__ __launch_bounds__(kSysThreads) void k_system_solve(int N, int nw, con
     for (int j = k + 1; j < N; ++j) s = sub(s, mul(mk(Ar(k, j), Ai(k, j)), mk(xr(j), xi(j))));
     s = cdiv(s, mk(Ar(k, k), Ai(k, k)));
     xr(k) = s.r; xi(k) = s.i;
-    st(Xi + (size_t)k * nw + b, s);
+    st(Xi + (size_t)k * nw + b, ok ? s : mk(__builtin_nan(""), __builtin_nan("")));
   }
 }
 
@@ -976,16 +980,19 @@ __global__ __launch_bounds__(64) void k_system_solve_reg(int nw, const rh_c128* 
     zload(0, A);
 #pragma unroll
     for (int i = 0; i < 6; ++i) x[i] = ld(F + (size_t)i * nw + b);
-    lu_solve<6>(A, x);
+    const bool ok = lu_solve<6>(A, x);     // a zero pivot: NaN rows (the reference raises LinAlgError)
+    const cd bad = mk(__builtin_nan(""), __builtin_nan(""));
     if (live)
 #pragma unroll
-      for (int i = 0; i < 6; ++i) st(Xi + (size_t)i * nw + b, x[i]);
+      for (int i = 0; i < 6; ++i) st(Xi + (size_t)i * nw + b, ok ? x[i] : bad);
   } else {
     // X = A^-1 K12 goes column by column to a lane-private LDS slab [36][re, im][64 lanes], so
     // A (factored) and S never occupy registers together
     __shared__ double xs[36 * 2 * 64];
     const int ln = threadIdx.x;
     cd y[6];
+    // a zero pivot in A or in S (a singular first block included) makes lu_factor's reciprocal pivot NaN,
+    // and every one of the 12 rows comes out NaN through the arithmetic below: no flag is carried
     {
       cd A[6][6];
       int pa[6];
@@ -1277,17 +1284,22 @@ __global__ __launch_bounds__(kArrRespThreads) void k_array_resp(ArrayArgs a) {
       cd A[6][6], x[6];
       excite(0, x);
       zload(0, A);
-      lu_solve<6>(A, x);
+      // a zero pivot: NaN rows for this bin, and through add_stats a NaN PSD and RMS for the case
+      const bool ok = lu_solve<6>(A, x);
+      const cd bad = mk(__builtin_nan(""), __builtin_nan(""));
       if (live)
   #pragma unroll
         for (int i = 0; i < 6; ++i) {
-          st(Xo + (size_t)i * nw + b, x[i]);
-          if (stats) add_stats(i, b, x[i]);
+          const cd xo = ok ? x[i] : bad;
+          st(Xo + (size_t)i * nw + b, xo);
+          if (stats) add_stats(i, b, xo);
         }
     } else {
       static_assert(NF == 2, "k_array_resp: one or two FOWTs");
       // X = A^-1 K12 column by column to a lane-private LDS slab [36][re, im][lanes]
       constexpr int T = kArrRespThreads;
+      // a zero pivot in A or in S: lu_factor's reciprocal pivot is NaN and all 12 rows come out NaN through
+      // the arithmetic below (and through add_stats the bin's PSD and the case's RMS); no flag is carried
       cd y[6];
       {
         cd A[6][6];

@@ -208,6 +208,11 @@ class Model:
                     Fws[i][ih] = Fws[i][ih] + fowt._f2nd_dev.to(torch.complex128)
                 Xi[ih] = self._system_solve(Zs, [Fw[ih] for Fw in Fws])
         self.Xi = Xi.cpu().numpy()
+        if np.isnan(self.Xi).any():
+            # the array solve stores NaN in the rows of a bin whose elimination met an exactly zero
+            # pivot (every fixed point above passed _check_pass, so nothing else leaves NaN here);
+            # the reference's solve raises there (raft/raft_model.py:1065)
+            raise np.linalg.LinAlgError("Singular matrix")
         self._xi_dev_all = Xi
         for i, fowt in enumerate(self.fowtList):
             xi_i = Xi[:, 6 * i:6 * i + 6, :].contiguous()
@@ -977,6 +982,10 @@ class Model:
         FOWTs with potSecOrder=2 add their .12d QTF's force to each sea state's excitation
         (:903-904, :1059-1061; f2nd_mean [n, N, 6]).
         Returns Xi [n, 6N, nw], iters / status [n, N], psd [n, N, 6, nw], std [n, N, 6], zeta.
+        A (case, bin) whose coupled solve meets an exactly zero pivot (a singular Z_sys, or for two
+        FOWTs a singular first block Z_1 + K_11) comes back with NaN in all its 6N rows of Xi, and that
+        case's psd bin and std are NaN: the batch is not interrupted and nothing is raised here (the
+        reference, and Model.solveDynamics, raise LinAlgError for such a case).
         prepared: prepareArrayBatch(cases) of an earlier call (then `cases` is not needed).
         marks: optional two timing events recorded around the fixed-point launch (bench).
         statics=True solves every case at its own mean-offset pose, as analyzeCases does: the offsets
@@ -1112,7 +1121,8 @@ class Model:
 
     def _array_extra_sea_states(self, P, res, X, out, keep):
         """Step 3 of analyzeArrayBatch: the further sea states of every case (one excitation and
-        one coupled-solve launch for all of them), Xi_waves and the statistics over all rows."""
+        one coupled-solve launch for all of them), Xi_waves and the statistics over all rows.  As in
+        step 2, a singular (sea state, bin) returns NaN rows, which its case's psd / std inherit."""
         import torch
         nf, n, nw = self.nFOWT, P["n"], self.nw
         dds, dev, seas, nws = P["dds"], P["dev"], P["seas"], P["nws"]

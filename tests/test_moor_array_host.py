@@ -33,6 +33,8 @@ def lib():
     L.rh_moor_array_eval_host.restype = None
     L.rh_array_statics_solve_host.argtypes = [_p] * 14
     L.rh_array_statics_solve_host.restype = None
+    L.rh_moor_array_lu_host.argtypes = [_p, _i, _i, _i]
+    L.rh_moor_array_lu_host.restype = _i
     return L
 
 
@@ -298,6 +300,37 @@ def test_old_refusals_stand():
         m.solveStaticsBatch([dict(C.CASES["wave"])])
     with pytest.raises(NotImplementedError):
         m.analyzeCasesBatch([dict(C.CASES["wave"])], statics=True)
+
+
+# ------------------------------------------------------------------------------ dense solve
+@pytest.mark.parametrize("n", [3, 6, 12, 24])
+@pytest.mark.parametrize("nrhs", [1, 6])
+def test_arr_lu_solve_matches_lapack(lib, n, nrhs):
+    """arr_lu_solve (the n x n solve with several right-hand sides behind the free-point and
+    condensation steps) against numpy.linalg.solve, as test_moor_host.test_solve6_matches_lapack does
+    for solve6: rows scaled over nine decades and permuted from a row-dominant order (so the pivot
+    search exchanges rows at most steps), a zero entry, a row stride ld > n + nrhs whose padding must
+    come back untouched, and a singular matrix that returns false."""
+    rng = np.random.default_rng(100 * n + nrhs)
+    ld = n + nrhs + 3
+    for _ in range(20):
+        A = rng.normal(size=[n, n]) + 4.0 * np.sqrt(n) * np.eye(n)
+        A = A[rng.permutation(n)] * 10 ** rng.uniform(-3, 6, size=[n, 1])
+        A[rng.integers(n), rng.integers(n)] = 0.0
+        B = rng.normal(size=[n, nrhs])
+        M = np.full([n, ld], 7.25)
+        M[:, :n], M[:, n:n + nrhs] = A, B
+        assert lib.rh_moor_array_lu_host(M.ctypes.data, n, nrhs, ld) == 1
+        ref = np.linalg.solve(A, B)
+        assert np.all(M[:, n + nrhs:] == 7.25)
+        assert np.abs(M[:, n:n + nrhs] - ref).max() <= 1e-12 * np.linalg.cond(A) * np.abs(ref).max()
+    M = np.full([n, ld], 7.25)
+    M[:, :n] = rng.normal(size=[n, n])
+    M[:, n // 2] = 0.0                      # a zero column: an exactly zero pivot at step n // 2
+    M[:, n:n + nrhs] = rng.normal(size=[n, nrhs])
+    assert lib.rh_moor_array_lu_host(M.ctypes.data, n, nrhs, ld) == 0
+    M[:, :n] = 0.0
+    assert lib.rh_moor_array_lu_host(M.ctypes.data, n, nrhs, ld) == 0
 
 
 # ------------------------------------------------------------------------------ ABI

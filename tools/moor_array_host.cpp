@@ -38,6 +38,12 @@ extern "C" void rh_moor_aline_host(const double* A, const double* B, double L, d
   out[15] = s.TA, out[16] = s.TB, out[17] = s.HF, out[18] = s.VF, out[19] = s.iters, out[20] = s.status;
 }
 
+// arr_lu_solve in place: M [n][ld] holds the matrix in its first n columns and the nrhs right-hand
+// sides (the solutions on return) in the columns after them; 1 = solved, 0 = zero pivot
+extern "C" int rh_moor_array_lu_host(double* M, int n, int nrhs, int ld) {
+  return rh::moor::arr_lu_solve(M, n, nrhs, ld) ? 1 : 0;
+}
+
 // rh_moor_array_eval of one record at npose poses [npose][nb][6]; warm [npose][nl][2] and fre
 // [npose][nf][3] in/out; F [npose][6nb], K [npose][6nb][6nb], T [npose][2nl], J [npose][2nl][6nb] or null
 extern "C" void rh_moor_array_eval_host(const int* rec_i, const double* rec_d, const double* pt, const double* ln,
