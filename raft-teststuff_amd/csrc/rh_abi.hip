@@ -98,9 +98,7 @@ namespace {
 thread_local std::string g_err;
 #ifdef RH_VARIANTS
 constexpr int kGroupCases = 2;   // lock-step width of k_solve_grp
-#else
-constexpr int kGroupCases = 1;   // no grouped kernel in the shipped library: group_start is ignored
-#endif
+// the variant k_solve_pair's tunables
 #ifndef RH_PAIR_RA
 #define RH_PAIR_RA 2
 #endif
@@ -117,6 +115,9 @@ constexpr bool kPairHold = RH_PAIR_HOLD;   // k_solve_pair keeps the unrelaxed i
 #define RH_PAIR_PB 2
 #endif
 constexpr int kPairPB = RH_PAIR_PB;   // bins per lane in phase A at 1024 threads
+#else
+constexpr int kGroupCases = 1;   // no grouped kernel in the shipped library: group_start is ignored
+#endif
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -149,6 +150,23 @@ int check_design(const rh_design& d, bool need_tables, bool need_uhat = true) {
   if (need_tables && ((need_uhat && !d.uhat) || !d.finer || !d.kproj || d.nhead < 1))
     return fail(RH_EINVAL, "design: wave tables missing (call rh_wave_tables first)");
   if (!(d.dw > 0)) return fail(RH_EINVAL, "design: dw must be > 0");
+  return RH_OK;
+}
+
+// The designs of a batched call: at least one, each of them valid (check_design), all on one frequency
+// grid.  nn and nm are the largest node and member counts (LDS layouts, the Bmat stride).
+struct Batch {
+  int nw, nn, nm;
+};
+int check_batch(const char* who, const rh_design* designs, int ndesign, bool need_tables, bool need_uhat, Batch& b) {
+  if (ndesign < 1) return fail(RH_EINVAL, "%s: ndesign=%d", who, ndesign);
+  b = {designs[0].nw, 0, 0};
+  for (int i = 0; i < ndesign; ++i) {
+    if (int r = check_design(designs[i], need_tables, need_uhat)) return r;
+    if (designs[i].nw != b.nw) return fail(RH_EINVAL, "%s: all designs must share nw", who);
+    b.nn = designs[i].nn > b.nn ? designs[i].nn : b.nn;
+    b.nm = designs[i].nm > b.nm ? designs[i].nm : b.nm;
+  }
   return RH_OK;
 }
 
@@ -454,7 +472,6 @@ extern "C" {
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,
                    const rh_solve_out* out, rh_stream stream) {
   if (!ctx || !designs || !cases || !out) return fail(RH_EINVAL, "rh_solve_cases: null argument");
-  if (ndesign < 1) return fail(RH_EINVAL, "rh_solve_cases: ndesign=%d", ndesign);
   if (cases->ncase < 0) return fail(RH_EINVAL, "rh_solve_cases: ncase=%d", cases->ncase);
   if (cases->ncase == 0) return RH_OK;
   if (!cases->design || !cases->head || !cases->spectrum || !cases->Hs || !cases->Tp || !cases->gamma)
@@ -463,18 +480,14 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
     return fail(RH_EINVAL, "rh_solve_cases: Xi_last, iters and status outputs are required");
   if (!out->Xi && (out->psd || out->std || out->rao))
     return fail(RH_EINVAL, "rh_solve_cases: psd, std and rao need the Xi output");
-  if (!out->Xi && designs[0].nw > rh_solve_noxi_max_bins())
-    return fail(RH_EINVAL, "rh_solve_cases: grids beyond %d bins need the Xi output", rh_solve_noxi_max_bins());
   if (cases->nIter < 0) return fail(RH_EINVAL, "rh_solve_cases: nIter=%d", cases->nIter);
   if (cases->first_iter < 0 || cases->first_iter > cases->nIter)
     return fail(RH_EINVAL, "rh_solve_cases: first_iter=%d outside [0, nIter=%d]", cases->first_iter, cases->nIter);
-  const int nw = designs[0].nw;
-  int nnmax = 0;
-  for (int i = 0; i < ndesign; ++i) {
-    if (int r = check_design(designs[i], true, false)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "rh_solve_cases: all designs must share nw");
-    if (designs[i].nn > nnmax) nnmax = designs[i].nn;
-  }
+  Batch b;
+  if (int r = check_batch("rh_solve_cases", designs, ndesign, true, false, b)) return r;
+  const int nw = b.nw, nnmax = b.nn, nmmax = b.nm;
+  if (!out->Xi && nw > rh_solve_noxi_max_bins())
+    return fail(RH_EINVAL, "rh_solve_cases: grids beyond %d bins need the Xi output", rh_solve_noxi_max_bins());
   RH_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   if (int r = stage_designs(ctx, designs, ndesign, s)) return r;
@@ -484,8 +497,6 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
   a.o = *out;
   a.bmat_nn = nnmax;
   a.all_axial = ctx->all_axial ? 1 : 0;
-  int nmmax = 0;
-  for (int i = 0; i < ndesign; ++i) nmmax = designs[i].nm > nmmax ? designs[i].nm : nmmax;
 #ifdef RH_VARIANTS
   // Grouped path (rh_solve_grp.hip): kGroupCases cases of one (design, heading) per workgroup.
   // (It does not report the convergence margin: with out->margin the ungrouped kernels run.)
@@ -530,15 +541,12 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
   };
   // Fast path (rh_solve.hip): XiLast in LDS, 512 threads per case (256 for nw <= 256), nw <= 1024.
   if (nw <= 2 * rh::kLT && !ctx->force_general) {
-#ifndef RH_SMALL_GRID_128
-#define RH_SMALL_GRID_128 1
-#endif
     // nw <= 256 on 128 threads x 2 bins (x 1 bin for nw <= 128), B_drag summed without the
     // per-node image (rh_solve.hip), four cases per CU while a workgroup's LDS stays within
-    // 40 KB: C4 0.544-0.554 ms against 0.586-0.590 ms for 256 threads x 1 bin
-    // (-DRH_SMALL_GRID_128=0).  The kernel depends on nw only, never on the batch's node counts,
+    // 40 KB: C4 0.544-0.554 ms against 0.586-0.590 ms for 256 threads x 1 bin.
+    // The kernel depends on nw only, never on the batch's node counts,
     // so the bits of a case do not depend on which designs share its launch.
-    if (RH_SMALL_GRID_128 && nw <= rh::kLT / 2) {
+    if (nw <= rh::kLT / 2) {
       const int nb128 = nw <= rh::kLT / 4 ? 1 : 2;
       const size_t lsm128 = rh::solve_lds_smem(nnmax, nmmax, nb128, rh::kLT / 4, true);
       if (lsm128 <= kMaxLds) {
@@ -608,14 +616,9 @@ int rh_heading_response_ext(rh_ctx* ctx, const rh_design* designs, int ndesign, 
   if (!ctx || !designs || !design_idx || !head || !zeta || !B_drag || !Bmat || !Xi)
     return fail(RH_EINVAL, "rh_heading_response: null argument");
   if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "ncase=%d", ncase);
-  if (ndesign < 1) return fail(RH_EINVAL, "rh_heading_response: ndesign=%d", ndesign);
-  const int nw = designs[0].nw;
-  int nnmax = 0;
-  for (int i = 0; i < ndesign; ++i) {
-    if (int r = check_design(designs[i], true)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "rh_heading_response: all designs must share nw");
-    if (designs[i].nn > nnmax) nnmax = designs[i].nn;
-  }
+  Batch b;
+  if (int r = check_batch("rh_heading_response", designs, ndesign, true, true, b)) return r;
+  const int nw = b.nw, nnmax = b.nn;
   if (bmat_nn == 0) bmat_nn = nnmax;
   if (bmat_nn < nnmax)
     return fail(RH_EINVAL, "rh_heading_response: Bmat row stride %d < %d nodes of a design passed", bmat_nn, nnmax);
@@ -641,13 +644,9 @@ int rh_wave_excitation(rh_ctx* ctx, const rh_design* designs, int ndesign, int n
   if (!ctx || !designs || !design_idx || !head || !zeta || !Bmat || !F)
     return fail(RH_EINVAL, "rh_wave_excitation: null argument");
   if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "ncase=%d", ncase);
-  const int nw = designs[0].nw;
-  int nnmax = 0;
-  for (int i = 0; i < ndesign; ++i) {
-    if (int r = check_design(designs[i], true)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "rh_wave_excitation: all designs must share nw");
-    if (designs[i].nn > nnmax) nnmax = designs[i].nn;
-  }
+  Batch b;
+  if (int r = check_batch("rh_wave_excitation", designs, ndesign, true, true, b)) return r;
+  const int nw = b.nw, nnmax = b.nn;
   RH_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   if (int r = stage_designs(ctx, designs, ndesign, s)) return r;
@@ -787,6 +786,21 @@ int rh_system_solve_batch(rh_ctx* ctx, int ncase, int nf, int nw, const rh_c128*
   return RH_OK;
 }
 
+namespace {
+// k_array_resp of nf FOWTs, one workgroup per case; a grid beyond the workgroup's threads takes several bins per thread
+void launch_array_resp(int nf, int nw, hipStream_t s, const rh::ArrayArgs& a) {
+  const dim3 g(a.ncase), gr(rh::kArrRespThreads);
+  const bool multi = nw > rh::kArrRespThreads;
+  if (nf == 1) {
+    if (multi) hipLaunchKernelGGL((rh::k_array_resp<1, true>), g, gr, 0, s, a);
+    else hipLaunchKernelGGL((rh::k_array_resp<1, false>), g, gr, 0, s, a);
+  } else {
+    if (multi) hipLaunchKernelGGL((rh::k_array_resp<2, true>), g, gr, 0, s, a);
+    else hipLaunchKernelGGL((rh::k_array_resp<2, false>), g, gr, 0, s, a);
+  }
+}
+}  // namespace
+
 int rh_array_response(rh_ctx* ctx, const rh_design* designs, int ndesign, int nf, int ncase, const int* design_idx,
                       const int* head, const double* zeta, const double* B_drag, const double* Bmat, const double* K,
                       rh_c128* Xi, rh_stream stream) {
@@ -803,15 +817,9 @@ int rh_array_response_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, 
   if ((psd || std_) && !(dw > 0)) return fail(RH_EINVAL, "rh_array_response_stats: dw=%g", dw);
   if (nf < 1 || nf > 2) return fail(RH_EINVAL, "rh_array_response: nf=%d (supported: 1, 2)", nf);
   if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "rh_array_response: ncase=%d", ncase);
-  if (ndesign < 1) return fail(RH_EINVAL, "rh_array_response: ndesign=%d", ndesign);
-  const int nw = designs[0].nw;
-  int nn = 0, nmmax = 0;   // nn: the largest node count (the Bmat stride and the LDS layout)
-  for (int i = 0; i < ndesign; ++i) {
-    if (int r = check_design(designs[i], true)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "rh_array_response: all designs must share nw");
-    nn = designs[i].nn > nn ? designs[i].nn : nn;
-    nmmax = designs[i].nm > nmmax ? designs[i].nm : nmmax;
-  }
+  Batch b;
+  if (int r = check_batch("rh_array_response", designs, ndesign, true, true, b)) return r;
+  const int nn = b.nn, nmmax = b.nm;   // nn: the largest node count (the Bmat stride and the LDS layout)
   const size_t lsm = rh::array_exc_smem(nn, nmmax);
   if (lsm > kMaxLds)
     return fail(RH_EINVAL, "rh_array_response: %d nodes / %d members need %zu B of LDS", nn, nmmax, lsm);
@@ -820,20 +828,11 @@ int rh_array_response_stats(rh_ctx* ctx, const rh_design* designs, int ndesign, 
   if (int r = stage_designs(ctx, designs, ndesign, s)) return r;
   rh::ArrayArgs a{staged_designs(ctx), ncase, design_idx, head, zeta, B_drag, Bmat, K, Xi, nn, nmmax, dw, psd, std_,
                   order};
-  const dim3 ge(ncase * nf), g(ncase);   // excitation per (case, FOWT), then the solve (+ statistics) per case
-  const bool multi = nw > rh::kArrRespThreads;
-  const dim3 gr(rh::kArrRespThreads);
-  if (nf == 1) {
-    hipLaunchKernelGGL(rh::k_array_exc<1>, ge, dim3(rh::kArrExcThreads), lsm, s, a);
-    RH_HIP(hipGetLastError());
-    if (multi) hipLaunchKernelGGL((rh::k_array_resp<1, true>), g, gr, 0, s, a);
-    else hipLaunchKernelGGL((rh::k_array_resp<1, false>), g, gr, 0, s, a);
-  } else {
-    hipLaunchKernelGGL(rh::k_array_exc<2>, ge, dim3(rh::kArrExcThreads), lsm, s, a);
-    RH_HIP(hipGetLastError());
-    if (multi) hipLaunchKernelGGL((rh::k_array_resp<2, true>), g, gr, 0, s, a);
-    else hipLaunchKernelGGL((rh::k_array_resp<2, false>), g, gr, 0, s, a);
-  }
+  const dim3 ge(ncase * nf);   // excitation per (case, FOWT), then the solve (+ statistics) per case
+  if (nf == 1) hipLaunchKernelGGL(rh::k_array_exc<1>, ge, dim3(rh::kArrExcThreads), lsm, s, a);
+  else hipLaunchKernelGGL(rh::k_array_exc<2>, ge, dim3(rh::kArrExcThreads), lsm, s, a);
+  RH_HIP(hipGetLastError());
+  launch_array_resp(nf, b.nw, s, a);
   RH_HIP(hipGetLastError());
   return designs_used(ctx, s);
 }
@@ -849,26 +848,14 @@ static int array_solve_stats(const char* who, rh_ctx* ctx, const rh_design* desi
   if (K_stride != 0 && (!K || K_stride < 36LL * nf * nf))
     return fail(RH_EINVAL, "%s: K_stride=%lld (0, or >= %d with a K)", who, K_stride, 36 * nf * nf);
   if (ncase <= 0) return ncase == 0 ? RH_OK : fail(RH_EINVAL, "%s: ncase=%d", who, ncase);
-  if (ndesign < 1) return fail(RH_EINVAL, "%s: ndesign=%d", who, ndesign);
-  const int nw = designs[0].nw;
-  for (int i = 0; i < ndesign; ++i) {
-    if (int r = check_design(designs[i], false)) return r;
-    if (designs[i].nw != nw) return fail(RH_EINVAL, "%s: all designs must share nw", who);
-  }
+  Batch b;
+  if (int r = check_batch(who, designs, ndesign, false, true, b)) return r;
   RH_HIP(hipSetDevice(ctx->device));
   hipStream_t s = (hipStream_t)stream;
   if (int r = stage_designs(ctx, designs, ndesign, s)) return r;
   rh::ArrayArgs a{staged_designs(ctx), ncase, design_idx, nullptr, nullptr, B_drag, nullptr, K, Xi, 0, 0, dw, psd, std_,
                   nullptr, K_stride};
-  const dim3 g(ncase), gr(rh::kArrRespThreads);
-  const bool multi = nw > rh::kArrRespThreads;
-  if (nf == 1) {
-    if (multi) hipLaunchKernelGGL((rh::k_array_resp<1, true>), g, gr, 0, s, a);
-    else hipLaunchKernelGGL((rh::k_array_resp<1, false>), g, gr, 0, s, a);
-  } else {
-    if (multi) hipLaunchKernelGGL((rh::k_array_resp<2, true>), g, gr, 0, s, a);
-    else hipLaunchKernelGGL((rh::k_array_resp<2, false>), g, gr, 0, s, a);
-  }
+  launch_array_resp(nf, b.nw, s, a);
   RH_HIP(hipGetLastError());
   return designs_used(ctx, s);
 }
@@ -987,13 +974,7 @@ static int qtf_launch(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double*
       const bool split = blocks <= RH_KAY_SPLIT_MAX_TILES(ctx->ncu);
       const int per = split ? rh::lk_tiles<rh::kKayP>() : rh::lk_tiles<1>();
       int nkb = (blocks + per - 1) / per, nly = 18 + q->nq + q->nmq;
-#if RH_ABL_LK_NOKAY    // timing ablation: no Kim & Yue tiles (wrong results)
-      nkb = 0;
-#endif
       if (cached) nkb = 0;   // their tile sums KS are in the workspace already
-#if RH_ABL_LK_NOCOEF   // timing ablation: no coefficient blocks (wrong results)
-      nly = 0;
-#endif
       if (split)
         hipLaunchKernelGGL(rh::k_qtf_lk<rh::kKayP>, dim3(nkb + nbx * nly), dim3(rh::kLkThreads), 0, s, *q, wk, M66, t0,
                            blocks, nkb, bx0, nbx);

@@ -769,145 +769,15 @@ __device__ __forceinline__ void lcoef_block(const rh_qtf_design& q, const QtfWor
 // ---------------------------------------------------------------------------------------
 // Complex GEMM steps of one 16 x 16 tile: A[m = i1][k] (lane l holds A[l & 15][4 s + (l >> 4)]),
 // B[k][n = i2] (B[4 s + (l >> 4)][l & 15]).  Three real MFMAs per step (Gauss):
-// P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi); Re = P1 - P2, Im = P3 - P1 - P2.  nsteps is a
-// multiple of 4: the loads of the next four steps are in flight while the MFMAs of the current
-// four run.
-#ifndef RH_QTF_PF
-#define RH_QTF_PF 4   // k-steps per operand batch (tools/ubench variant: 8)
-#endif
-#ifndef RH_QTF_CHAIN
-#define RH_QTF_CHAIN 1   // 1: the bilinear and potential-channel k-steps as one operand stream (cgemm_steps2)
-#endif
-#ifndef RH_QTF_SPLIT
-#define RH_QTF_SPLIT 0   // 1: even / odd k-steps in two accumulator sets (tools/ubench variant)
-#endif
-__device__ __forceinline__ void cgemm_steps(const rh_c128* __restrict__ A, const rh_c128* __restrict__ B, size_t step,
-                                            int nsteps, d4& p1, d4& p2, d4& p3) {
-  constexpr int PF = RH_QTF_PF;
-#if RH_QTF_SPLIT
-  d4 q1 = {0, 0, 0, 0}, q2 = q1, q3 = q1;
-#endif
-  cd a[PF], b[PF];
-#pragma unroll
-  for (int j = 0; j < PF; ++j) {
-    const int sj = (PF > 4 && j >= nsteps) ? nsteps - 1 : j;
-    a[j] = ld(A + sj * step);
-    b[j] = ld(B + sj * step);
-  }
-#pragma unroll 1
-  for (int s = 0; s < nsteps; s += PF) {
-    cd an[PF], bn[PF];
-    const bool more = s + PF < nsteps;
-    if (more) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        // nsteps is a multiple of 4: a deeper batch (variant) stops at the last step
-        const int sj = (PF > 4 && s + PF + j >= nsteps) ? nsteps - 1 : s + PF + j;
-        an[j] = ld(A + sj * step);
-        bn[j] = ld(B + sj * step);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < PF; j += 2) {
-      if (PF > 4 && s + j >= nsteps) break;   // uniform (variant only)
-      p1 = mfma64(a[j].r, b[j].r, p1);
-      p2 = mfma64(a[j].i, b[j].i, p2);
-      p3 = mfma64(a[j].r + a[j].i, b[j].r + b[j].i, p3);
-#if RH_QTF_SPLIT   // two accumulator sets (six independent MFMA chains): the round-2/3 order
-      q1 = mfma64(a[j + 1].r, b[j + 1].r, q1);
-      q2 = mfma64(a[j + 1].i, b[j + 1].i, q2);
-      q3 = mfma64(a[j + 1].r + a[j + 1].i, b[j + 1].r + b[j + 1].i, q3);
-#else              // one chain per product, the k-step order of k_qtf_gemm32: sharded == whole, bit for bit
-      p1 = mfma64(a[j + 1].r, b[j + 1].r, p1);
-      p2 = mfma64(a[j + 1].i, b[j + 1].i, p2);
-      p3 = mfma64(a[j + 1].r + a[j + 1].i, b[j + 1].r + b[j + 1].i, p3);
-#endif
-    }
-    if (more) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        a[j] = an[j];
-        b[j] = bn[j];
-      }
-    }
-  }
-#if RH_QTF_SPLIT
-  p1 += q1;
-  p2 += q2;
-  p3 += q3;
-#endif
-}
-
+// P1 = Ar Br, P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi); Re = P1 - P2, Im = P3 - P1 - P2.
+//
 // The bilinear steps (A1, B1: n1 steps, into p) and the potential channel's (A2, B2: n2 steps,
 // into c) as one operand stream: the channel's first batch is loaded while the last bilinear
-// batch runs, instead of after it.  Each accumulator sees its k-steps in the same order as with
-// two cgemm_steps calls (the same bits).  n1 and n2 are multiples of 4.
-__device__ __forceinline__ void cgemm_steps2(const rh_c128* __restrict__ A1, const rh_c128* __restrict__ B1, int n1,
-                                             const rh_c128* __restrict__ A2, const rh_c128* __restrict__ B2, int n2,
-                                             size_t step, d4& p1, d4& p2, d4& p3, d4& c1, d4& c2, d4& c3) {
-  constexpr int PF = 4;
-  const int nt = n1 + n2;
-  auto src = [&](int s, const rh_c128*& a, const rh_c128*& b) {   // operands of k-step s (uniform)
-    if (s < n1) {
-      a = A1 + s * step;
-      b = B1 + s * step;
-    } else {
-      a = A2 + (s - n1) * step;
-      b = B2 + (s - n1) * step;
-    }
-  };
-  cd a[PF], b[PF];
-  {
-    const rh_c128 *pa, *pb;
-    src(0, pa, pb);
-#pragma unroll
-    for (int j = 0; j < PF; ++j) {
-      a[j] = ld(pa + j * step);
-      b[j] = ld(pb + j * step);
-    }
-  }
-#pragma unroll 1
-  for (int s = 0; s < nt; s += PF) {
-    cd an[PF], bn[PF];
-    const bool more = s + PF < nt;
-    if (more) {
-      const rh_c128 *pa, *pb;
-      src(s + PF, pa, pb);
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        an[j] = ld(pa + j * step);
-        bn[j] = ld(pb + j * step);
-      }
-    }
-    if (s < n1) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        p1 = mfma64(a[j].r, b[j].r, p1);
-        p2 = mfma64(a[j].i, b[j].i, p2);
-        p3 = mfma64(a[j].r + a[j].i, b[j].r + b[j].i, p3);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        c1 = mfma64(a[j].r, b[j].r, c1);
-        c2 = mfma64(a[j].i, b[j].i, c2);
-        c3 = mfma64(a[j].r + a[j].i, b[j].r + b[j].i, c3);
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        a[j] = an[j];
-        b[j] = bn[j];
-      }
-    }
-  }
-}
-
-// cgemm_steps2 with a ring of operand registers instead of a double buffer: k-step s + j is
-// consumed from slot j, which is then refilled with k-step s + PF + j, so PF steps stay in flight
-// with half the operand registers (the kernel fits 128 VGPRs: four waves per SIMD).  Same MFMA
-// order per accumulator, the same bits.
+// batch runs, instead of after it.  n1 and n2 are multiples of 4.  The operands live in a ring of
+// registers, not a double buffer: k-step s + j is consumed from slot j, which is then refilled with
+// k-step s + PF + j, so PF steps stay in flight with half the operand registers (the kernel fits 128
+// VGPRs: four waves per SIMD).  One MFMA chain per product, every accumulator's k-steps in order (the
+// k-step order of k_qtf_gemm32: sharded == whole, bit for bit; two accumulator sets break that).
 __device__ __forceinline__ void cgemm_ring2(const rh_c128* __restrict__ A1, const rh_c128* __restrict__ B1, int n1,
                                             const rh_c128* __restrict__ A2, const rh_c128* __restrict__ B2, int n2,
                                             size_t step, d4& p1, d4& p2, d4& p3, d4& c1, d4& c2, d4& c3) {
@@ -1024,9 +894,6 @@ __device__ __forceinline__ void qtf_tile_of(int t, int nt, int& T1, int& T2) {
 #ifndef RH_QTF_GDOF
 #define RH_QTF_GDOF 2   // DOFs per k_qtf_gemm workgroup: 2 (4 waves, 3 workgroups per tile) or 3 (6 waves, 2)
 #endif
-#ifndef RH_QTF_RING
-#define RH_QTF_RING 1   // 1: operand ring (cgemm_ring2), 0: double buffer (cgemm_steps2)
-#endif
 constexpr int kGD = RH_QTF_GDOF;
 constexpr int kGThreads = 128 * kGD;
 static_assert(6 % kGD == 0, "the DOFs split evenly over a tile's workgroups");
@@ -1069,11 +936,7 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(RH_QT
       const double bt = q.beta * kDeg2Rad, cb = cos(bt), sb = sin(bt);
       const int i1 = min(i1b + (x >> 4), n2 - 1), i2 = min(i2b + (x & 15), n2 - 1);
       cd sp, sm;
-#if RH_ABL_G_NOPOT   // timing ablation (wrong results)
-      sp = cd{q.w2[i1], tkh[x >> 4]}; sm = cd{q.w2[i2], tkh[16 + (x & 15)]};
-#else
       qtf_pot_scalars(q.w2[i1], q.k2[i1], tkh[x >> 4], q.w2[i2], q.k2[i2], tkh[16 + (x & 15)], cb, sb, h, g, sp, sm);
-#endif
       pscal[0][x] = sp.r;
       pscal[1][x] = sp.i;
       pscal[2][x] = sm.r;
@@ -1085,25 +948,9 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(RH_QT
   const int k0 = half == 0 ? 0 : ns0, nk = half == 0 ? ns0 : ns - ns0;
   d4 p1 = {0, 0, 0, 0}, p2 = p1, p3 = p1;
   d4 c1 = {0, 0, 0, 0}, c2 = c1, c3 = c1;   // potential channel c = half
-#if RH_QTF_CHAIN && RH_QTF_RING && !RH_ABL_G_NOBIL && !RH_ABL_G_NOPCH
   cgemm_ring2(wk.L + ((size_t)d * kp + 4 * k0 + kr) * n2p + i1b + mr, wk.R + ((size_t)4 * k0 + kr) * n2p + i2b + mr, nk,
               wk.Lp + (((size_t)half * 6 + d) * kq + kr) * n2p + i1b + mr,
               wk.Rp + ((size_t)half * kq + kr) * n2p + i2b + mr, kq / 4, step, p1, p2, p3, c1, c2, c3);
-#elif RH_QTF_CHAIN && !RH_ABL_G_NOBIL && !RH_ABL_G_NOPCH
-  cgemm_steps2(wk.L + ((size_t)d * kp + 4 * k0 + kr) * n2p + i1b + mr, wk.R + ((size_t)4 * k0 + kr) * n2p + i2b + mr, nk,
-               wk.Lp + (((size_t)half * 6 + d) * kq + kr) * n2p + i1b + mr,
-               wk.Rp + ((size_t)half * kq + kr) * n2p + i2b + mr, kq / 4, step, p1, p2, p3, c1, c2, c3);
-#else
-#if !RH_ABL_G_NOBIL   // timing ablation: no bilinear GEMM (wrong results)
-  if (nk > 0)
-    cgemm_steps(wk.L + ((size_t)d * kp + 4 * k0 + kr) * n2p + i1b + mr, wk.R + ((size_t)4 * k0 + kr) * n2p + i2b + mr,
-                step, nk, p1, p2, p3);
-#endif
-#if !RH_ABL_G_NOPCH   // timing ablation: no potential-channel GEMM (wrong results)
-  cgemm_steps(wk.Lp + (((size_t)half * 6 + d) * kq + kr) * n2p + i1b + mr,
-              wk.Rp + ((size_t)half * kq + kr) * n2p + i2b + mr, step, kq / 4, c1, c2, c3);
-#endif
-#endif
   const d4 mre = p1 - p2, mim = p3 - p1 - p2, cre = c1 - c2, cim = c3 - c1 - c2;
   if (half == 1) {
 #pragma unroll
@@ -1131,14 +978,6 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(RH_QT
                                part[dl][8 + r][lane], part[dl][12 + r][lane], pscal[0][e], pscal[1][e], pscal[2][e],
                                pscal[3][e], ks[(2 * d) * 256 + ek], ks[(2 * d + 1) * 256 + ek]);
     rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6 + d;
-#if RH_ABL_G_NOSTORE   // timing ablation: no stores (wrong results)
-    if (Qf.r == 1.2345e300) st(up, Qf);
-    continue;
-#endif
-#if RH_ABL_G_NOMIRROR  // timing ablation: upper triangle only (wrong results)
-    st(up, Qf);
-    continue;
-#endif
     if (!mirror) {
       st(up, Qf);
     } else if (i1 == i2) {
@@ -1159,10 +998,6 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(RH_QT
 // keeps per element sum sre and sum sre p over the member's rows, and adds
 // phase x [s0 pf; s x pf] (the rows' translateForce3to6DOF) to the tile's LDS sum in member
 // order.  The next row's operands are loaded while the current row is reduced.
-
-#ifndef RH_KAY_SPLIT
-#define RH_KAY_SPLIT 1   // waves per member of the variants' k_qtf_kay (k_qtf_lk picks per call)
-#endif
 constexpr int kKayM = 4;                   // Kim & Yue members per round
 // A member's rows are summed in kKayP contiguous parts, and the parts' sums added in part order,
 // whether one wave takes all the parts one after the other (S = 1) or each part has a wave of
@@ -1172,13 +1007,11 @@ constexpr int kKayP = 2;
 static_assert(kKayP == 2, "kay_tile: the part sums are added as P0 + P1");
 template <int S>
 constexpr int kay_threads() { return 64 * kKayM * S; }
-constexpr int kKayS = RH_KAY_SPLIT;
-constexpr int kKayThreads = kay_threads<kKayS>();
-// One pair tile's Kim & Yue sums by a group of kKayW waves (tid 0 .. kKayThreads - 1 of the
+// One pair tile's Kim & Yue sums by a group of kKayM S waves (tid 0 .. kay_threads<S>() - 1 of the
 // group) into acc[12][256]; live = false: the group has no tile and only joins the block's
 // barriers (every group of a block runs the same member rounds).  Every __syncthreads here is
 // a whole-block barrier: the caller's block is made of such groups only.  A member's rows are
-// split into kKayS contiguous parts, one per wave; the parts' row sums meet in part order
+// split into S contiguous parts, one per wave; the parts' row sums meet in part order
 // (psg, LDS) before the member's phase is applied.
 template <int S>
 __device__ __forceinline__ void kay_tile(const rh_qtf_design& q, const QtfWork& wk, int T1, int T2, bool live, int tid,

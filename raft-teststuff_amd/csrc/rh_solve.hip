@@ -51,22 +51,6 @@ constexpr int kLW = kLT / 64;     // waves per case workgroup
 #endif
 constexpr int kRingA1 = RH_RING_A; // wave-table prefetch depth (nodes) of phase A
 constexpr int kRingC = RH_RING_C; // ... of phase C (one bin per pass: less work per node)
-#ifndef RH_ONE_VOTE
-#define RH_ONE_VOTE 0                 // 1: one barrier (LDS flag word) for the three end-of-iteration votes
-#endif
-#ifndef RH_OVERLAP
-#define RH_OVERLAP 1                  // 1: no barrier vote between phase C and the next phase A (single-pass kernels)
-#endif
-#ifndef RH_STATS_C
-#define RH_STATS_C 1                  // 1: PSD / RAO / RMS sums formed where phase C stores Xi (no read-back)
-#endif
-#ifndef RH_XI_STORE
-#define RH_XI_STORE 1                 // 0: per-entry stores of passing entries; 1: while the iteration may be final; 2: traffic floor (A/B)
-#endif
-#define XI_STORE_MODE RH_XI_STORE
-#ifndef RH_A_PAIR
-#define RH_A_PAIR 1                   // 1: phase-A sums of two nodes per butterfly (tbfly4)
-#endif
 constexpr int kAxC = 4;               // axial wave-table rows phase C holds at a time (its own path, beside the ring)
 #ifndef RH_JOINT_C
 #define RH_JOINT_C 1                  // 1: k_solve_lds<2, 512> forms both bins' excitation in one phase-C node sweep
@@ -74,9 +58,6 @@ constexpr int kAxC = 4;               // axial wave-table rows phase C holds at 
 constexpr bool kJointC = RH_JOINT_C != 0;
 #ifndef RH_BATCH_B
 #define RH_BATCH_B 1                  // 1: phase B reads its LDS operands in batches ahead of their uses; 0: one by one (A/B)
-#endif
-#ifndef RH_JOINT_PARK
-#define RH_JOINT_PARK 1               // 1: bin 1's excitation waits in global memory for bin 0's solve; 0: in registers (A/B)
 #endif
 // The joint sweep's ring: the kRingC slots hold one (node, bin) each, so it is kRingC / 2 nodes deep
 // with the same rows in flight (and the same registers) as the one-bin ring.
@@ -89,12 +70,6 @@ static_assert(kRingC % 2 == 0, "the joint phase-C ring pairs its slots");
 // node-indexed LDS tables that the loops read carry one zero row, row nn, for all of them (56
 // bytes: the C4 kernel's four workgroups per CU have about 300 bytes of LDS to spare).
 constexpr int kGhost = 1;
-#ifndef RH_A_QUAD
-#define RH_A_QUAD 1                   // 1: phase-A transverse sums of four nodes per butterfly (tbfly8; ring depth 4)
-#endif
-#ifndef RH_LDS_LANE_BRANCH
-#define RH_LDS_LANE_BRANCH 0          // 1: the round-2 per-lane `continue` before the solve (A/B only)
-#endif
 
 // |a|^2 as fma(re, re, im im), said outright.  Left to the compiler (abs2), which of the two products is
 // fused follows from the order of the sum's operands in its graph, and an unrelated change in phase B
@@ -222,7 +197,7 @@ __device__ __forceinline__ Bfly4 bfly4_lane(int lane) {
   b.vi8 = lane >= 8 ? -1 : 4 * b.f0 + 2 * b.f1 + b.f2;
   return b;
 }
-// Eight wave sums at once (RH_A_QUAD: the transverse sums of four nodes): three transposing
+// Eight wave sums at once (the transverse sums of a phase-A ring round's four nodes): three transposing
 // stages (partners i^1, i^2, i^7), 8 -> 4 -> 2 -> 1 values, then i^15 and the rows as tbfly4:
 // the same partners in the same order for every value, 10 exchanges.
 __device__ __forceinline__ double tbfly8(const double (&u)[8], const Bfly4& L) {
@@ -398,10 +373,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   constexpr int NBT = NB * NP;                     // bins per thread over all passes
   constexpr bool GX = NP > 1;                      // XiLast in the Xi_last block, not in LDS
   constexpr int kRingA = GX ? 3 : kRingA1;
-  // PSD / RAO / RMS sums formed in phase C (RH_STATS_C) by the 512-thread kernels; the SER
-  // kernels (C4's fixed point: no response output) keep them in the epilogue
-  constexpr bool kStatsC = RH_STATS_C && (XI_STORE_MODE == 1) && !SER && NB > 1;
-#if RH_OVERLAP && !defined(RH_VARIANTS)
+  // PSD / RAO / RMS sums formed in phase C, where it stores Xi (no read-back), by the 512-thread
+  // kernels; the SER kernels (C4's fixed point: no response output) keep them in the epilogue
+  constexpr bool kStatsC = !SER && NB > 1;
+#ifndef RH_VARIANTS
   constexpr bool kOv = !GX;                        // the vote deferred into the next phase A (below)
 #else
   constexpr bool kOv = false;                      // (variants: the two-pass launch stops mid-loop)
@@ -559,9 +534,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       cd SQ = mk(0, 0), S1 = mk(0, 0), S2 = mk(0, 0), T1 = mk(0, 0), T2 = mk(0, 0);
       auto load1 = [&](cd (&K)[2], int n) {
         const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
-#if RH_ABL_C_NOLOAD
-        if (n >= kRingC) return;
-#endif
 #pragma unroll
         for (int p = 0; p < 2; ++p) K[p] = bld(bK, vj, so + (unsigned)(p + 1) * nw16);
       };
@@ -614,11 +586,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           const double* A = al + 6 * (n + 1 < nn ? n + 1 : nn);
           A1 = A[1]; A2 = A[2]; A3 = A[3]; A4 = A[4];
         }
-#if RH_ABL_C_NOCOMP
-        S1 = add(S1, K[0]); S2 = add(S2, K[1]);
-        load1(K, n + kRingC);
-        return;
-#endif
         S1 = add(S1, scl(K[0], a1));
         S2 = add(S2, scl(K[1], a2));
         T1 = add(T1, scl(K[0], a3));
@@ -912,9 +879,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       // after it (nothing couples s_q to s_1 and s_2).
       auto load_node = [&](cd (&K)[2][NB], int n) {
         const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;
-#if RH_ABL_A_NOLOAD   // timing ablation: the ring keeps its first nodes (wrong results)
-        if (n >= kRingA) return;
-#endif
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
@@ -934,11 +898,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       // this lane's partial sums over its bins of |s_1|^2, |s_2|^2 for one node
       auto node_sums = [&](const cd (&K)[2][NB], double t, double& s1, double& s2) {
         s1 = s2 = 0;
-#if RH_ABL_A_NOCOMP   // timing ablation: consume the loads with one add each (wrong results)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) { s1 += K[0][j].r + K[0][j].i; s2 += K[1][j].r + K[1][j].i; }
-        return;
-#endif
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
           const double z = bz[j];
@@ -948,11 +907,12 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           s2 += abs2(sp2);
         }
       };
-      // RH_A_QUAD: the sums of a ring round's four nodes reduced together (tbfly8; ring depth 4);
-      // RH_A_PAIR alone: those of nodes 2k and 2k + 1 (tbfly4; even ring depth); with either, the
-      // axial sums of four nodes per tbfly4; otherwise tbfly3 per node, and per three axial nodes
-      constexpr bool kPair = RH_A_PAIR && (kRingA % 2 == 0);
-      constexpr int kAx = kPair ? 4 : 3;   // axial nodes per butterfly
+      // Ring depth 4 (one pass): the sums of a ring round's four nodes reduced together (tbfly8) and the
+      // axial sums of four nodes per tbfly4; depth 3 (two-pass GX): tbfly3 per node, and per three axial
+      // nodes.  (Two nodes per butterfly measured slower than four)
+      static_assert(kRingA == 4 || kRingA == 3, "phase A reduces a round of 4 nodes (tbfly8) or single nodes at depth 3");
+      constexpr bool kQuad = kRingA == 4;
+      constexpr int kAx = kQuad ? 4 : 3;   // axial nodes per butterfly
       const int nA = skip_a ? 0 : nn;   // no node steps when iteration 0's sums came from k_a0_sums
       // The first kAx axial rows are requested before the ring's, so they arrive behind the
       // transverse loop; a design with more axial nodes waits once per further kAx of them.
@@ -967,12 +927,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         __builtin_amdgcn_sched_barrier(0);
       }
       int m = -1, mnext = 0;
-      double h1 = 0.0, h2 = 0.0;   // (kPair) the even node's sums
-      constexpr bool kQuad = RH_A_QUAD && kPair && kRingA == 4;
       [[maybe_unused]] double u8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (kQuad) the sums of a round's nodes
-      // (kPair) the butterfly's lane flags: formed here, live through the node loops only
+      // (kQuad) the butterfly's lane flags: formed here, live through the node loops only
       // (lane_here is not hoisted out of the iteration loop)
-      const Bfly4 bl = bfly4_lane(kPair ? lane_here() : 0);
+      const Bfly4 bl = bfly4_lane(kQuad ? lane_here() : 0);
       // Whole ring rounds: the last one ends in ghost nodes (the last node's rows again), whose sums
       // are reduced like any other's and written nowhere.  node n's t is read a node ahead.
       double tn = nt[0];
@@ -1002,26 +960,12 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
               const double tot = tbfly8(u8, bl);
               if (bl.vi8 >= 0 && n + (bl.vi8 >> 1) < nA) {
                 double& rr = red[((n + (bl.vi8 >> 1)) * 3 + 1 + (bl.vi8 & 1)) * LW + wv_s];
-                rr = (GX && p > 0) ? rr + tot : tot;
-              }
-            }
-          } else if constexpr (kPair) {
-            if ((r & 1) == 0) {   // held for the odd node
-              h1 = s1; h2 = s2;
-            } else {
-              const double tot = tbfly4(h1, h2, s1, s2, bl);
-              if (bl.vi >= 0 && nr - 1 + (bl.vi >> 1) < nA) {
-                double& rr = red[((nr - 1 + (bl.vi >> 1)) * 3 + 1 + (bl.vi & 1)) * LW + wv_s];
                 rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
               }
             }
           } else {
             const int ln = lane_here();
-#if RH_ABL_A_NOBFLY
-            const double tot = s1 + s2;
-#else
             const double tot = tbfly3(s1, s2, 0.0, ln);
-#endif
             if (ln < 3 && tbfly3_index(ln) < 2 && nr < nA) {
               double& rr = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
               rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
@@ -1053,7 +997,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         }
         int vi;
         double tot;
-        if constexpr (kPair) {
+        if constexpr (kQuad) {
           tot = tbfly4(q[0], q[1], q[2], q[3], bl);
           vi = bl.vi;
         } else {
@@ -1269,11 +1213,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         sflag[3 + ((it + 1) & 1)] = 0;
       }
     }
-#if !RH_JOINT_PARK
-    cd FR[6];   // (A/B: bin 1's excitation kept in registers across bin 0's solve)
-#pragma unroll
-    for (int c = 0; c < 6; ++c) FR[c] = mk(0.0, 0.0);
-#endif
 #pragma unroll 1
     for (int j = 0; j < NBT; ++j) {
       // per-bin scalars picked without dynamic register indexing (the loop is not unrolled,
@@ -1300,27 +1239,17 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           excite2(F2);
 #pragma unroll
           for (int c = 0; c < 6; ++c) F[c] = F2[0][c];
-#if RH_JOINT_PARK
           if (bj + LT < nw) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) st(PK + LT + c * nw, F2[1][c]);
           }
-#else
-#pragma unroll
-          for (int c = 0; c < 6; ++c) FR[c] = F2[1][c];
-#endif
         } else {
-#if RH_JOINT_PARK
 #pragma unroll
           for (int c = 0; c < 6; ++c) F[c] = mk(0.0, 0.0);   // pad lanes: zeta = 0 gave F = 0
           if (okj) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) F[c] = ld(PK + c * nw);
           }
-#else
-#pragma unroll
-          for (int c = 0; c < 6; ++c) F[c] = FR[c];
-#endif
         }
       } else {
         excite(bj, F);
@@ -1337,15 +1266,11 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
 #ifdef RH_PROF
       tc_exc += tc1 - tc0;
 #endif
-#if RH_LDS_LANE_BRANCH
-      if (!okj) continue;
-#else
       // No lane branch around the solve (a per-lane `continue` here let the compiler's spills
       // run under a partial EXEC mask in the general kernel): only a wave whose
       // every lane is past the grid skips it (uniform); pad lanes of the last wave solve the
       // clamped last bin with a zero right-hand side (zeta = 0, x = 0 exactly) and store nothing.
       if (!__builtin_amdgcn_ballot_w64(okj)) continue;
-#endif
       const int b = bj;
       const double w = lw[b];
       cd Z[6][6];
@@ -1408,13 +1333,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         const bool gt = okj && n2 * tD > tN * d2;
         tN = gt ? n2 : tN;
         tD = gt ? d2 : tD;
-        [[maybe_unused]] const bool pass = n2 < td * td;
-#if RH_XI_STORE == 0
-        // (round 4: an entry stored whenever it passed its own test or at the last iteration)
-        if (okj && (GX || Xo) && (pass || last_it)) st_nt(Xo + c * nw + b, x);
-#elif RH_XI_STORE == 2
-        if (okj && (GX || Xo) && last_it) st_nt(Xo + c * nw + b, x);   // traffic floor (A/B only: wrong Xi)
-#endif
         if (okj && XP) st(XP + c * nw + b, xlast);
         // XiLast = 0.2 XiLast + 0.8 Xi  (:991), only consumed if not converged (pads: 0)
         const cd xr = add(scl(xlast, 0.2), scl(x, 0.8));
@@ -1424,7 +1342,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           xl[c * NWP + b] = xr;
         }
       }
-#if RH_XI_STORE == 1
       // The unrelaxed iterate leaves the kernel only as the output of the case's final
       // iteration: the one whose test every (bin, DOF) passed, or the last allowed one
       // (raft/raft_model.py:996-1000).  So the bin's six entries are stored only while this
@@ -1462,7 +1379,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           for (int c = 0; c < 6; ++c) st_nt(Xo + c * nw + b, F[c]);
         }
       }
-#endif
 #ifdef RH_PROF
       tc_sol += clock64() - tc1;
 #endif
@@ -1524,27 +1440,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       iters = it + 1;
       break;
     } else {
-#if RH_ONE_VOTE
-    // One barrier for the three votes: each wave ORs its flag bits (1 = a bin not converged,
-    // 2 = NaN, 4 = singular) into this iteration's LDS word; tid 0 clears the other word for
-    // the next iteration (everyone has read it: it was last read before this iteration's
-    // phase-A barrier).
-    {
-      const unsigned long long bn = __builtin_amdgcn_ballot_w64(!my_ok), bx = __builtin_amdgcn_ballot_w64(my_nan),
-                               bs = __builtin_amdgcn_ballot_w64(my_sing);
-      const int bits = (bn ? 1 : 0) | (bx ? 2 : 0) | (bs ? 4 : 0);
-      if (lane == 0 && bits) atomicOr(&sflag[it & 1], bits);
-    }
-    __syncthreads();
-    const int fl = sflag[it & 1];
-    if (tid == 0) sflag[(it + 1) & 1] = 0;
-    const int all_ok = !(fl & 1), any_nan = fl & 2, any_sing = fl & 4;
-    if (a.o.margin && tid == 0) {   // mred is rewritten only after the next phase-A barrier
-      double mx = mred[0];
-      for (int w = 1; w < LW; ++w) mx = fmax(mx, mred[w]);
-      margin = closer_call(margin, mx - tol);
-    }
-#else
+    // (three barrier votes; one barrier with an LDS flag word moved the launch not at all)
     const int all_ok = __syncthreads_and(my_ok ? 1 : 0);
     if (a.o.margin && tid == 0) {   // mred is rewritten only after the next phase-A barrier
       double mx = mred[0];
@@ -1553,7 +1449,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     }
     const int any_nan = __syncthreads_or(my_nan ? 1 : 0);
     const int any_sing = __syncthreads_or(my_sing ? 1 : 0);
-#endif
     PROF_T(ta4);
     PROF_ADD(5, ta4 - ta3);
     if (any_nan) {

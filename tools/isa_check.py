@@ -66,8 +66,10 @@ BRANCH = re.compile(r"^\s*s_(cbranch_\w+|branch)\s+(\.LBB\w+)")
 STREAM = re.compile(r"^\s*(buffer_load|global_load)")
 
 
-def compile_asm(defines=()):
-    """Device assembly of every translation unit (compiled in parallel), concatenated."""
+def compile_asm(defines=(), csrc=None):
+    """Device assembly of every translation unit (compiled in parallel), concatenated.  csrc: the source
+    directory (default: this tree's; tools/asm_same.py passes that of another revision)."""
+    csrc = csrc or G.CSRC
     fd, path = tempfile.mkstemp(suffix=".s")
     os.close(fd)
     procs, parts = [], []
@@ -75,7 +77,7 @@ def compile_asm(defines=()):
         part = path + "." + unit + ".s"
         parts.append(part)
         procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags,
-                                       *defines, "--offload-device-only", "-S", "-o", part, os.path.join(G.CSRC, unit)],
+                                       *defines, "--offload-device-only", "-S", "-o", part, os.path.join(csrc, unit)],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     for p in procs:
         _, err = p.communicate()

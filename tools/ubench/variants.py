@@ -3,86 +3,75 @@ case-solve time to its phases on the GPU.  The ablated libraries give wrong answ
 construction; tools/ubench/time_solve.py only times them (per executed iteration)."""
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-CSRC = os.path.join(ROOT, "raft-teststuff_amd", "csrc")
+sys.path.insert(0, ROOT)
+import __graft_entry__ as G  # noqa: E402  (the build's translation units and their flags)
+REL_CSRC = os.path.relpath(G.CSRC, ROOT)
+CSRC = G.CSRC
 
+# name: [(file under csrc, anchor, replacement)]; every anchor occurs exactly once in its file
+# (tests/test_variants_tool.py).  The entries from cNoLoad on are the timing ablations that were `#if
+# RH_ABL_<PHASE>_<WHAT>` blocks of the kernels (DESIGN.md §5 records their numbers).  The first letter
+# says which driver times a library: q, k, g the QTF ones (run_qtf_variants.sh, run_qtf_mfma_variants.sh).
 EDITS = {
-    "qNoKay": [("rh_qtf.hip", "    if (qm(q, RH_QM_KAY, m) != 0.0) {", "    if (qm(q, RH_QM_KAY, m) == 12345.0) {")],
-    "qNoNodes": [("rh_qtf.hip", "    for (int n = n0; n < n1; ++n) {\n      const rh_c128* T = wk.node", "    for (int n = n0; n < n0; ++n) {\n      const rh_c128* T = wk.node")],
-    # MFMA QTF path (rh_qtf_mfma.hip) ablations
-    "kNoEpi": [("rh_qtf_mfma.hip", "        if (wl) {   // waterline term (:1133-1149): Re(-i kap A) = kap Im(A)\n          sre = kap * ca[r];\n        } else {",
-                "        if (true) {\n          sre = kap * (ca[r] + cbk[r]);\n        } else {")],
-    "kNoMfma": [("rh_qtf_mfma.hip", "          ca = mfma64(va[s], vr[s], ca);\n          cbk = mfma64(vb[s], vr[s], cbk);",
-                 "          ca[0] += va[s] * vr[s];\n          cbk[0] += vb[s] * vr[s];")],
-    "kNoFinal": [("rh_qtf_mfma.hip", "  if (a1 >= n2 || a2 >= n2 || a2 < a1) return;", "  if (a1 >= -1) return;")],
-    "kNoRows": [("rh_qtf_mfma.hip", "    for (int ir = rlo; ir < rhi; ++ir) {", "    for (int ir = rlo; ir < rlo; ++ir) {")],
-    "gNoMfmaOps": [("rh_qtf_mfma.hip", "      p1 = mfma64(a[j].r, b[j].r, p1);\n      p2 = mfma64(a[j].i, b[j].i, p2);\n      p3 = mfma64(a[j].r + a[j].i, b[j].r + b[j].i, p3);",
-                    "      p1[0] += a[j].r * b[j].r;\n      p2[0] += a[j].i * b[j].i;\n      p3[0] += a[j].r * b[j].i;")],
-    "gFixedLoads": [("rh_qtf_mfma.hip", "        an[j] = ld(A + (s + 4 + j) * step);\n        bn[j] = ld(B + (s + 4 + j) * step);",
-                     "        an[j] = ld(A + j * step);\n        bn[j] = ld(B + j * step);")],
-    "gNoEpi": [("rh_qtf_mfma.hip", "    if ((w1 != w2) && (k1 > 0) && (k2 > 0)) {   // second-order potential (raft/helpers.py:254-291)\n      const double kx = k1 * cb - k2 * cb",
-                "    if (w1 < -1.0) {\n      const double kx = k1 * cb - k2 * cb")],
-    "gNoPot": [("rh_qtf_mfma.hip", "  cgemm_steps(wk.Lp + ", "  if (nk < 0) cgemm_steps(wk.Lp + ")],
-    "gNoMain": [("rh_qtf_mfma.hip", "  if (nk > 0)\n    cgemm_steps(", "  if (nk < 0)\n    cgemm_steps(")],
-    "prof": [],          # unmodified source built with -DRH_PROF (phase cycle counters)
-    # nw <= 256 (C4): 128 threads x 2 bins per lane instead of 256 x 1 (half the reductions per bin)
-    "c4nb2": [("rh_abi.hip", "    const int nb = nw <= rh::kLT ? 1 : 2;\n", "    const int nb = (nw <= rh::kLT && nw > rh::kLT / 2) ? 1 : 2;\n"),
-              ("rh_abi.hip", "    const int lt = nw <= rh::kLT / 2 ? rh::kLT / 2 : rh::kLT;",
-               "    const int lt = nw <= rh::kLT / 2 ? rh::kLT / 4 : rh::kLT;"),
-              ("rh_abi.hip", "      if (lt < rh::kLT) hipLaunchKernelGGL((rh::k_solve_lds<1, rh::kLT / 2>), grid, block, lsm, s, a);",
-               "      if (lt < rh::kLT) hipLaunchKernelGGL((rh::k_solve_lds<2, rh::kLT / 4>), grid, block, lsm, s, a);")],
-    # phase C: the node's drag coefficients read from LDS one node ahead (registers)
-    "cPrefA": [("        int m = 0, mnext = nn > 0 ? mstart[1] : 0;\n",
-                "        int m = 0, mnext = nn > 0 ? mstart[1] : 0;\n"
-                "        double Ac0 = al[0], Ac1 = al[1], Ac2 = al[2], Ac3 = al[3], Ac4 = al[4];\n"),
-               ("          const double* A = al + 5 * n;\n"
-                "          const double A0 = A[0], A1 = A[1], A2 = A[2], A3 = A[3], A4 = A[4];\n",
-                "          const double A0 = Ac0, A1 = Ac1, A2 = Ac2, A3 = Ac3, A4 = Ac4;\n"
-                "          const double* An = al + 5 * (n + 1 < nn ? n + 1 : n);\n"
-                "          Ac0 = An[0]; Ac1 = An[1]; Ac2 = An[2]; Ac3 = An[3]; Ac4 = An[4];\n")],
-    "noLU": [("      my_sing |= !lu_solve<6>(Z, F);", "      F[0] = add(F[0], Z[0][0]);")],
-    "stXo": [("        st_nt(Xo + c * nw + b, x);", "        st(Xo + c * nw + b, x);")],
-    "noXo": [("        st_nt(Xo + c * nw + b, x);", "        if (x.r == 1234.5) st(Xo + c * nw + b, x);")],
     "qNoPot": [("rh_qtf.hip", "    if (pot_on && rz <= 0) {", "    if (pot_on && rz <= -1e300) {")],
     "qNoKY": [("rh_qtf.hip", "    for (int ir = NWV - 1 - wv; ir < q.nkr; ir += NWV) {", "    for (int ir = NWV - 1 - wv; ir < 0; ir += NWV) {")],
     "qNoRot": [("rh_qtf.hip", "    // (5) Rainey body-rotation terms (:1556-1575)\n    cd fr[3];\n    {", "    // (5) Rainey body-rotation terms (:1556-1575)\n    cd fr[3] = {vA[0], vA[1], vA[2]};\n    if (rz < -1e300) {")],
-    "qKyUnroll": [("rh_qtf.hip", "#pragma unroll 1\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, kay_omega(D1, D2, nn));",
-                   "#pragma unroll\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, kay_omega(D1, D2, nn));"),
-                  ("rh_qtf.hip", "#pragma unroll 1\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, scl(kay_omega",
-                   "#pragma unroll\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, scl(kay_omega")],
-    "qKyUnroll4": [("rh_qtf.hip", "#pragma unroll 1\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, scl(kay_omega",
-                   "#pragma unroll 4\n        for (int nn = 0; nn <= 10; ++nn) s = add(s, scl(kay_omega")],
-    "noA": [("      for (int n = 0; n < nn; n += 3) {\n        step(KA, n);\n        if (n + 1 < nn) step(KB, n + 1);",
-             "      for (int n = 0; n < 0; n += 3) {\n        step(KA, n);\n        if (n + 1 < nn) step(KB, n + 1);")],
-    "noC": [("        for (int n = 0; n < nn; n += 3) {\n          step(KA, n);",
-             "        for (int n = 0; n < 0; n += 3) {\n          step(KA, n);")],
+    # MFMA QTF path (rh_qtf_mfma.hip)
+    "kNoMfma": [("rh_qtf_mfma.hip", "          ca = mfma64(va[s], vr[s], ca);\n          cbk = mfma64(vb[s], vr[s], cbk);",
+                 "          ca[0] += va[s] * vr[s];\n          cbk[0] += vb[s] * vr[s];")],
+    "prof": [],          # unmodified source built with -DRH_PROF (phase cycle counters)
+    # k_solve_lds, phase C: the ring keeps its first nodes / the loads consumed with one add each
+    "cNoLoad": [("rh_solve.hip", "        const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;\n#pragma unroll\n        for (int p = 0; p < 2; ++p) K[p] = bld(bK, vj, so + (unsigned)(p + 1) * nw16);",
+                      "        const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;\n        if (n >= kRingC) return;\n#pragma unroll\n        for (int p = 0; p < 2; ++p) K[p] = bld(bK, vj, so + (unsigned)(p + 1) * nw16);")],
+    "cNoComp": [("rh_solve.hip", "        S1 = add(S1, scl(K[0], a1));\n        S2 = add(S2, scl(K[1], a2));\n        T1 = add(T1, scl(K[0], a3));",
+                      "        S1 = add(S1, K[0]); S2 = add(S2, K[1]);\n        load1(K, n + kRingC);\n        return;\n"
+                      "        S1 = add(S1, scl(K[0], a1));\n        S2 = add(S2, scl(K[1], a2));\n        T1 = add(T1, scl(K[0], a3));")],
+    # ... phase A: the same two, and the node sums without their butterfly (the two-pass kernel's tbfly3 only)
+    "aNoLoad": [("rh_solve.hip", "      auto load_node = [&](cd (&K)[2][NB], int n) {\n        const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;\n",
+                      "      auto load_node = [&](cd (&K)[2][NB], int n) {\n        const unsigned so = (unsigned)(n < nn ? n : nn - 1) * 3u * nw16;\n        if (n >= kRingA) return;\n")],
+    "aNoComp": [("rh_solve.hip", "        s1 = s2 = 0;\n#pragma unroll\n        for (int j = 0; j < NB; ++j) {\n          const double z = bz[j];",
+                      "        s1 = s2 = 0;\n#pragma unroll\n        for (int j = 0; j < NB; ++j) { s1 += K[0][j].r + K[0][j].i; s2 += K[1][j].r + K[1][j].i; }\n        return;\n"
+                      "#pragma unroll\n        for (int j = 0; j < NB; ++j) {\n          const double z = bz[j];")],
+    "aNoBfly": [("rh_solve.hip", "            const double tot = tbfly3(s1, s2, 0.0, ln);", "            const double tot = s1 + s2;")],
+    # k_qtf_gemm: no pair scalars of the potential, no bilinear / no potential-channel k-steps, no stores,
+    # the upper triangle only
+    "gNoPot": [("rh_qtf_mfma.hip", "      qtf_pot_scalars(q.w2[i1], q.k2[i1], tkh[x >> 4], q.w2[i2], q.k2[i2], tkh[16 + (x & 15)], cb, sb, h, g, sp, sm);",
+                     "      sp = cd{q.w2[i1], tkh[x >> 4]}; sm = cd{q.w2[i2], tkh[16 + (x & 15)]};")],
+    "gNoBil": [("rh_qtf_mfma.hip", "wk.R + ((size_t)4 * k0 + kr) * n2p + i2b + mr, nk,\n", "wk.R + ((size_t)4 * k0 + kr) * n2p + i2b + mr, 0,\n")],
+    "gNoPch": [("rh_qtf_mfma.hip", "kq / 4, step, p1, p2, p3, c1, c2, c3);", "0, step, p1, p2, p3, c1, c2, c3);")],
+    "gNoStore": [("rh_qtf_mfma.hip", "    rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6 + d;\n    if (!mirror) {",
+                       "    rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6 + d;\n    if (Qf.r == 1.2345e300) st(up, Qf);\n    continue;\n    if (!mirror) {")],
+    "gNoMirror": [("rh_qtf_mfma.hip", "    rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6 + d;\n    if (!mirror) {",
+                        "    rh_c128* up = qtf + ((size_t)i1 * n2 + i2) * 6 + d;\n    st(up, Qf);\n    continue;\n    if (!mirror) {")],
+    # k_qtf_lk's launch: no Kim & Yue tiles / no coefficient blocks
+    "gNoKay": [("rh_abi.hip", "      if (cached) nkb = 0;   // their tile sums KS are in the workspace already\n", "      nkb = 0;\n")],
+    "gNoCoef": [("rh_abi.hip", "      int nkb = (blocks + per - 1) / per, nly = 18 + q->nq + q->nmq;\n", "      int nkb = (blocks + per - 1) / per, nly = 0;\n")],
 }
 
 
 def build(name, edits, flags=()):
+    """Copy the sources, apply the edits and build tools/ubench/var_<name>.so as the library itself is built."""
     tmp = tempfile.mkdtemp()
-    dst = os.path.join(tmp, "csrc")
-    shutil.copytree(CSRC, dst)
-    inc = os.path.join(tmp, "..", "include")
-    for e in edits:
-        fname, a, b = e if len(e) == 3 else ("rh_solve.hip", e[0], e[1])
-        p = os.path.join(dst, fname)
-        s = open(p).read()
-        assert a in s, (name, a[:60])
-        s = s.replace(a, b)
-        open(p, "w").write(s)
-    # rh_device.h includes ../../include/rafthip.h relative to csrc
-    os.makedirs(os.path.join(tmp, "x"), exist_ok=True)
-    shutil.move(dst, os.path.join(tmp, "x", "csrc"))
-    shutil.copytree(os.path.join(ROOT, "include"), os.path.join(tmp, "include"))
+    for rel in (REL_CSRC, "include", os.path.join("tools", "ubench", "variants_src")):   # (csrc includes the other two by relative path)
+        shutil.copytree(os.path.join(ROOT, rel), os.path.join(tmp, rel))
+    for fname, a, b in edits:
+        p = os.path.join(tmp, REL_CSRC, fname)
+        with open(p) as fh:
+            s = fh.read()
+        assert s.count(a) == 1, (name, fname, a[:60])
+        with open(p, "w") as fh:
+            fh.write(s.replace(a, b))
     out = os.path.join(ROOT, "tools", "ubench", f"var_{name}.so")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
-                    "-Wno-unused-result", *flags, "-o", out, os.path.join(tmp, "x", "csrc", "rh_abi.hip")], check=True)
-    shutil.rmtree(tmp)
+    csrc, G.CSRC = G.CSRC, os.path.join(tmp, REL_CSRC)   # compile_library: the shipped units and flags
+    try:
+        G.compile_library(out, list(flags))
+    finally:
+        G.CSRC = csrc
+        shutil.rmtree(tmp)
     print("built", out)
 
 

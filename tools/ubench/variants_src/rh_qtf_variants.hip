@@ -154,6 +154,11 @@ __global__ __launch_bounds__(512) void k_qtf_lcoef(rh_qtf_design q, QtfWork wk, 
 // The Kim & Yue sums of this rank's pair tiles (kay_tile), one tile per workgroup; the GEMM
 // epilogue adds them (before round 4 this kernel ran on a second stream beside k_qtf_lcoef +
 // k_qtf_gemm, with two event hand-offs and a final k_qtf_kay_sum launch).
+#ifndef RH_KAY_SPLIT
+#define RH_KAY_SPLIT 1   // waves per member (the shipped k_qtf_lk picks per call)
+#endif
+constexpr int kKayS = RH_KAY_SPLIT;
+constexpr int kKayThreads = kay_threads<kKayS>();
 __global__ __launch_bounds__(kKayThreads) __attribute__((amdgpu_waves_per_eu(RH_KAY_WPE))) void k_qtf_kay(
     rh_qtf_design q, QtfWork wk, int t0) {
   __shared__ double acc[12][256];
