@@ -3,8 +3,16 @@
 // Complex FP64 arithmetic in the order NumPy uses it, the register-resident partially
 // pivoted LU solve that replaces LAPACK zgesv (numpy.linalg.solve, raft/raft_model.py:947)
 // and wavefront reductions for 64-lane waves.
+// The arithmetic and the LU also compile for the host (g++, one "lane": tools/lu_host.cpp), so that
+// tests/test_lu_fma_host.py runs the very statements the kernels run.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define RH_DEV __device__ __forceinline__
+#else
+#include <cmath>
+#define RH_DEV inline
+#endif
 #include "../../include/rafthip.h"
 
 namespace rh {
@@ -13,7 +21,8 @@ struct cd {
   double r, i;
 };
 
-__device__ __forceinline__ cd mk(double r, double i) { return cd{r, i}; }
+RH_DEV cd mk(double r, double i) { return cd{r, i}; }
+#if defined(__HIPCC__)
 __device__ __forceinline__ cd ld(const rh_c128* p) {
   const double2 v = *reinterpret_cast<const double2*>(p);
   return cd{v.x, v.y};
@@ -27,18 +36,33 @@ __device__ __forceinline__ void st_nt(rh_c128* p, cd v) {
   __builtin_nontemporal_store(v.r, q);
   __builtin_nontemporal_store(v.i, q + 1);
 }
-__device__ __forceinline__ cd add(cd a, cd b) { return cd{a.r + b.r, a.i + b.i}; }
-__device__ __forceinline__ cd sub(cd a, cd b) { return cd{a.r - b.r, a.i - b.i}; }
-__device__ __forceinline__ cd mul(cd a, cd b) { return cd{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
-__device__ __forceinline__ cd scl(cd a, double s) { return cd{a.r * s, a.i * s}; }
+#endif
+RH_DEV cd add(cd a, cd b) { return cd{a.r + b.r, a.i + b.i}; }
+RH_DEV cd sub(cd a, cd b) { return cd{a.r - b.r, a.i - b.i}; }
+RH_DEV cd mul(cd a, cd b) { return cd{a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
+RH_DEV cd scl(cd a, double s) { return cd{a.r * s, a.i * s}; }
 // i*w*a  (NumPy: (1j*w)*a = (0,w)*(ar,ai))
-__device__ __forceinline__ cd iw(double w, cd a) { return cd{-w * a.i, w * a.r}; }
-__device__ __forceinline__ double abs2(cd a) { return a.r * a.r + a.i * a.i; }
-__device__ __forceinline__ double cabs(cd a) { return hypot(a.r, a.i); }
-__device__ __forceinline__ double cabs1(cd a) { return fabs(a.r) + fabs(a.i); }  // LAPACK dcabs1
+RH_DEV cd iw(double w, cd a) { return cd{-w * a.i, w * a.r}; }
+RH_DEV double abs2(cd a) { return a.r * a.r + a.i * a.i; }
+RH_DEV double cabs(cd a) { return hypot(a.r, a.i); }
+RH_DEV double cabs1(cd a) { return fabs(a.r) + fabs(a.i); }  // LAPACK dcabs1
+// a - l * u, the update of the LU below, in four FMAs: each component takes its two products into the
+// running value one after the other, l.r's first (two roundings).  The order is fixed here, not left to
+// contraction, which made mul, fma, add of sub(a, mul(l, u)): six instructions, three roundings a component.
+RH_DEV cd msub(cd a, cd l, cd u) {
+  return cd{__builtin_fma(l.i, u.i, __builtin_fma(-l.r, u.r, a.r)), __builtin_fma(-l.i, u.r, __builtin_fma(-l.r, u.i, a.i))};
+}
+// does any lane of the wave hold p (the host build has one lane)
+RH_DEV bool wave_any(bool p) {
+#if defined(__HIPCC__)
+  return __builtin_amdgcn_ballot_w64(p) != 0;
+#else
+  return p;
+#endif
+}
 
 // Smith's complex division (as LAPACK zladiv / C99), a / b.
-__device__ __forceinline__ cd cdiv(cd a, cd b) {
+RH_DEV cd cdiv(cd a, cd b) {
   if (fabs(b.i) <= fabs(b.r)) {
     const double e = b.i / b.r, f = b.r + b.i * e;
     return cd{(a.r + a.i * e) / f, (a.i - a.r * e) / f};
@@ -51,7 +75,7 @@ __device__ __forceinline__ cd cdiv(cd a, cd b) {
 // wins as in izamax) on an N x N complex system; A and x are overwritten, x = A^-1 x.
 // Returns false on an exactly zero pivot (LAPACK: info > 0 -> LinAlgError("Singular matrix")).
 template <int N>
-__device__ __forceinline__ bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
+RH_DEV bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -66,7 +90,7 @@ __device__ __forceinline__ bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
     // The row exchange is a chain of per-lane selects; skip it when no lane of the wave
     // pivots off the diagonal at this step (the common case for these impedance matrices).
     // Results are the same either way.
-    if (__builtin_amdgcn_ballot_w64(p != k) != 0) {
+    if (wave_any(p != k)) {
 #pragma unroll
       for (int i = k + 1; i < N; ++i) {
         const bool sw = (p == i);
@@ -91,15 +115,15 @@ __device__ __forceinline__ bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
     for (int i = k + 1; i < N; ++i) {
       const cd l = mul(A[i][k], rinv);
 #pragma unroll
-      for (int j = k + 1; j < N; ++j) A[i][j] = sub(A[i][j], mul(l, A[k][j]));
-      x[i] = sub(x[i], mul(l, x[k]));
+      for (int j = k + 1; j < N; ++j) A[i][j] = msub(A[i][j], l, A[k][j]);
+      x[i] = msub(x[i], l, x[k]);
     }
   }
 #pragma unroll
   for (int k = N - 1; k >= 0; --k) {
     cd s = x[k];
 #pragma unroll
-    for (int j = k + 1; j < N; ++j) s = sub(s, mul(A[k][j], x[j]));
+    for (int j = k + 1; j < N; ++j) s = msub(s, A[k][j], x[j]);
     x[k] = mul(s, A[k][k]);
   }
   return ok;
@@ -112,7 +136,7 @@ __device__ __forceinline__ bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
 // elimination (as lu_solve does in one pass).  Returns false on an exactly zero pivot, after which
 // the factorisation holds NaN and lu_apply returns NaN in every row.
 template <int N>
-__device__ __forceinline__ bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
+RH_DEV bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -125,7 +149,7 @@ __device__ __forceinline__ bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
     }
     ok = ok && (best != 0.0);
     piv[k] = p;
-    if (__builtin_amdgcn_ballot_w64(p != k) != 0) {
+    if (wave_any(p != k)) {
 #pragma unroll
       for (int i = k + 1; i < N; ++i) {
         const bool sw = (p == i);
@@ -150,16 +174,16 @@ __device__ __forceinline__ bool lu_factor(cd (&A)[N][N], int (&piv)[N]) {
       const cd l = mul(A[i][k], rinv);
       A[i][k] = l;
 #pragma unroll
-      for (int j = k + 1; j < N; ++j) A[i][j] = sub(A[i][j], mul(l, A[k][j]));
+      for (int j = k + 1; j < N; ++j) A[i][j] = msub(A[i][j], l, A[k][j]);
     }
   }
   return ok;
 }
 template <int N>
-__device__ __forceinline__ void lu_apply(const cd (&A)[N][N], const int (&piv)[N], cd (&x)[N]) {
+RH_DEV void lu_apply(const cd (&A)[N][N], const int (&piv)[N], cd (&x)[N]) {
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    if (__builtin_amdgcn_ballot_w64(piv[k] != k) != 0) {
+    if (wave_any(piv[k] != k)) {
 #pragma unroll
       for (int i = k + 1; i < N; ++i) {
         const bool sw = (piv[k] == i);
@@ -169,17 +193,18 @@ __device__ __forceinline__ void lu_apply(const cd (&A)[N][N], const int (&piv)[N
       }
     }
 #pragma unroll
-    for (int i = k + 1; i < N; ++i) x[i] = sub(x[i], mul(A[i][k], x[k]));
+    for (int i = k + 1; i < N; ++i) x[i] = msub(x[i], A[i][k], x[k]);
   }
 #pragma unroll
   for (int k = N - 1; k >= 0; --k) {
     cd s = x[k];
 #pragma unroll
-    for (int j = k + 1; j < N; ++j) s = sub(s, mul(A[k][j], x[j]));
+    for (int j = k + 1; j < N; ++j) s = msub(s, A[k][j], x[j]);
     x[k] = mul(s, A[k][k]);
   }
 }
 
+#if defined(__HIPCC__)
 // Raw buffer access: the 128-bit resource lives in SGPRs, each lane supplies one 32-bit byte
 // offset and the per-array / per-component part is a scalar offset.  This keeps the many
 // (array, DOF, bin) addresses of the case solve from being materialised as 64-bit VGPR pairs,
@@ -235,5 +260,7 @@ __device__ __forceinline__ int xcd_remap(int b, int G) {
   const int x = b & 7, q = G >> 3, r = G & 7;
   return x * q + (x < r ? x : r) + (b >> 3);
 }
+
+#endif  // __HIPCC__
 
 }  // namespace rh

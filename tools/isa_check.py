@@ -20,7 +20,8 @@ checks every kernel:
   * the compiler's VGPR and spilled-VGPR counts of every kernel (`vgpr=`, `spill=`), reported.
   * for the C2 kernel, the `s_waitcnt lgkmcnt` count of phase B (`phaseB_lgkm_waits=`): the section runs on
     one wave while seven wait, so its dependent LDS round trips are step time; reported (tests/test_isa_phase_b.py
-    gates it).
+    gates it), and its static FP64 instruction counts (`fp64_mul=`, `fp64_add=`, `fp64_fma=`), reported
+    (tests/test_isa_lu_fma.py holds the first two against the counts before the LU's updates were fused).
 Loops are found from the branch structure: a branch to a label that precedes it closes a loop
 [label, branch]; a loop that contains no other loop is innermost; it streams if it holds a
 buffer_load / global_load.
@@ -244,6 +245,20 @@ def phase_b_lgkm_waits(body):
     return sum(1 for i in range(bars[k], bars[k + 2]) if LGKM_WAIT.match(body[i]))
 
 
+FP64_OP = re.compile(r"^\s*v_(mul|add|fma)c?_f64(_e32|_e64|_dpp)?\s")
+
+
+def fp64_counts(body):
+    """Static counts (mul, add, fma) of a body's `v_mul_f64`, `v_add_f64` and `v_fma_f64` / `v_fmac_f64`: an unfused complex
+    multiply-subtract shows as 2 mul + 2 fma + 2 add where 4 fma do (tests/test_isa_lu_fma.py)."""
+    n = {"mul": 0, "add": 0, "fma": 0}
+    for ln in body:
+        m = FP64_OP.match(ln)
+        if m:
+            n[m.group(1)] += 1
+    return n["mul"], n["add"], n["fma"]
+
+
 def analyse(body):
     labels = {}
     for i, ln in enumerate(body):
@@ -326,6 +341,7 @@ def main():
         if any(k in dn for k in JOINT_C):
             nb = phase_b_lgkm_waits(body)
             rings += f" phaseB_lgkm_waits={'?' if nb is None else nb}"
+            rings += " fp64_mul=%d fp64_add=%d fp64_fma=%d" % fp64_counts(body)
         if verdict.startswith("FAIL"):
             fails.append(dn)
         rows.append(f"{dn:70s} hot={int(hot)} loops={r['loops']:3d} inner={r['inner']:3d} "
