@@ -124,12 +124,6 @@ typedef struct {
   const rh_c128* Xi_init; /* [ncase][6][nw] initial XiLast instead of XiStart, or NULL          */
   int first_iter;         /* initial value of the iteration counter (1 for the second pass of
                              potSecOrder=1, raft/raft_model.py:973-1000), normally 0         */
-  const int* group_start; /* optional [ngroup+1] device array of offsets into `order`: group g
-                             is order[group_start[g] .. group_start[g+1]), 1..rh_group_cases()
-                             cases that share design AND heading index, solved in lock-step by
-                             one workgroup.  Ignored when rh_group_cases() == 1 (the shipped
-                             library: one case per workgroup).  NULL -> one case per workgroup. */
-  int ngroup;
 } rh_cases;
 
 /* Outputs of rh_solve_cases (device buffers; NULL = not wanted). */
@@ -176,25 +170,12 @@ int rh_version(void);
  * drag or end drag, the others' axial terms being exact zeros: same bits either way),
  * 8 = automatic, with the two-bin fast path (512 < nw <= 1024) sweeping the nodes once per bin
  * for the excitation (by default one sweep forms both bins': same bits either way), 9 = 6 and 8.  Used by
- * the parity tests to cross-check the device paths on the same inputs.  (Builds with -DRH_VARIANTS, made by
- * tools/build_variants.sh for on-box A/B timing only, also accept 2..5: the lock-step grouped
- * kernel, the lane-pair kernel and the two-pass launch, all measured slower) */
+ * the parity tests to cross-check the device paths on the same inputs.  Any other value: RH_EINVAL. */
 int rh_set_solver(rh_ctx* ctx, int which);
-
-/* Iteration-0 sums as a batch GEMM on this context (not part of the reference API; default 0).
- * The shipped library accepts only 0 (every case forms them in its own workgroup) and refuses 1
- * with RH_EINVAL: k_a0_sums, which forms phase A of the first iteration of every case that starts
- * from XiStart as one MFMA launch, was measured slower on C2 and C4 and is built
- * only into variant libraries (tools/build_variants.sh, -DRH_VARIANTS), where 1 enables it. */
-int rh_set_a0(rh_ctx* ctx, int on);
 
 /* Largest grid (bins) rh_solve_cases can solve with rh_solve_out.Xi = NULL (the linearisation
  * only); larger grids keep their iterate in the Xi output and need it (RH_EINVAL otherwise). */
 int rh_solve_noxi_max_bins(void);
-
-/* Maximum cases per group of rh_cases.group_start: 1 in the shipped library (no grouped
- * kernel; group_start is then ignored). */
-int rh_group_cases(void);
 
 /* Waves per 64 (w1, w2) pairs in the QTF pair kernel on this context (not part of the
  * reference API): 1, 2, 4, or 0 (default: auto, currently 4 waves, the fastest measured
@@ -206,10 +187,7 @@ int rh_set_qtf_waves(rh_ctx* ctx, int waves);
 
 /* QTF pair-sum path of this context: 0 (default) = FP64 MFMA GEMMs on 16 x 16 pair tiles when
  * the grid is sorted (rh_qtf_design.order == 1), 1 = the per-pair kernel k_qtf_pairs (parity
- * cross-checks).  Variant libraries (tools/build_variants.sh) also take 2 = the GEMMs with
- * 32 x 32 tiles for a whole QTF and 3 = the GEMM coefficients (k_qtf_lcoef) and the Kim & Yue
- * sums (k_qtf_kay) as two launches (both measured slower, the same bits as 0); the shipped
- * library refuses them with RH_EINVAL. */
+ * cross-checks).  Any other value: RH_EINVAL. */
 int rh_set_qtf_path(rh_ctx* ctx, int path);
 
 /* Unit-amplitude wave kinematics and strip-theory inertial excitation per heading.

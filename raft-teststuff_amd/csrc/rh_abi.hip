@@ -22,15 +22,6 @@
 #include "rh_qtf_mfma.hip"
 #include "rh_solve.hip"        // k_solve_lds: only the two-pass <2, 512, false, 2> is instantiated here
 #include "rh_solve_launch.h"   // ... the single-pass ones live in rh_solve_fast.hip (max-ilp scheduler)
-#ifdef RH_VARIANTS
-// Opt-in solve kernels that were measured slower than k_solve_lds on C2: the
-// lock-step grouped kernel, the lane-pair kernel and the two-pass launch.  They are not part
-// of the shipped library; tools/build_variants.sh builds them for on-box A/B timing.
-#include "../../tools/ubench/variants_src/rh_solve_grp.hip"
-#include "../../tools/ubench/variants_src/rh_solve_pair.hip"
-#include "../../tools/ubench/variants_src/rh_a0.hip"            // k_a0_sums (rh_set_a0)
-#include "../../tools/ubench/variants_src/rh_qtf_variants.hip"  // k_qtf_gemm32, k_qtf_lcoef + k_qtf_kay (rh_set_qtf_path 2, 3)
-#endif
 #ifndef RH_KAY_SPLIT_MAX_TILES
 #define RH_KAY_SPLIT_MAX_TILES(ncu) (ncu)   // k_qtf_lk: one wave per part of a member's rows up to this many tiles
 #endif
@@ -61,28 +52,9 @@ struct rh_ctx {
   bool force_general = false;   // rh_set_solver(ctx, 1): always use k_solve_cases (parity cross-checks)
   bool all_axial = false;       // rh_set_solver(ctx, 6 / 9): k_solve_lds streams every node's axial row (cross-checks)
   bool split_c = false;         // rh_set_solver(ctx, 8 / 9): one phase-C sweep per bin (k_solve_lds_split; cross-checks)
-#ifdef RH_VARIANTS
-  bool a0 = false;              // rh_set_a0: iteration-0 phase A of the fast path as a batch GEMM (rh_a0.hip;
-                                // measured slower than the per-case phase A)
-  bool no_group = false;        // rh_set_solver(ctx, 2): ignore group_start (one case per workgroup)
-#ifndef RH_PAIR_ON
-#define RH_PAIR_ON 0
-#endif
-  bool use_pair = RH_PAIR_ON;   // rh_set_solver(ctx, 3): k_solve_pair instead of k_solve_lds (cross-checks)
-#ifndef RH_TWO_PASS
-#define RH_TWO_PASS 0
-#endif
-  bool two_pass = RH_TWO_PASS;  // k_solve_lds in two passes when a batch needs more than one round
-                                // (rh_set_solver(ctx, 5) on, 4 off; the default is RH_TWO_PASS)
-#endif
   int ncu = 0;                  // compute units of the device (rh_ctx_create)
   int qtf_waves = 0;            // rh_set_qtf_waves: waves per 64 QTF pairs in k_qtf_pairs (0 = auto)
   bool qtf_direct = false;      // rh_set_qtf_path(ctx, 1): the per-pair kernel even on a sorted grid
-#ifdef RH_VARIANTS
-  bool qtf_sep = false;         // rh_set_qtf_path(ctx, 3): k_qtf_lcoef and k_qtf_kay as two launches
-  bool qtf_t32 = false;         // rh_set_qtf_path(ctx, 2): 32 x 32 GEMM tiles for a whole QTF
-                                // (68.7 vs 57.0 us per C3 QTF)
-#endif
   // per-stream scratch of rh_wave_tables (per-node forces, k_wave_tables_nodes ->
   // k_wave_force_sum): one buffer per stream, so stream order alone protects its reuse
   struct Scratch {
@@ -96,28 +68,6 @@ struct rh_ctx {
 
 namespace {
 thread_local std::string g_err;
-#ifdef RH_VARIANTS
-constexpr int kGroupCases = 2;   // lock-step width of k_solve_grp
-// the variant k_solve_pair's tunables
-#ifndef RH_PAIR_RA
-#define RH_PAIR_RA 2
-#endif
-#ifndef RH_PAIR_RC
-#define RH_PAIR_RC 4
-#endif
-constexpr int kPairRA = RH_PAIR_RA;   // k_solve_pair wave-table prefetch depth, phase A (nodes)
-constexpr int kPairRC = RH_PAIR_RC;   // ... phase C
-#ifndef RH_PAIR_HOLD
-#define RH_PAIR_HOLD 0
-#endif
-constexpr bool kPairHold = RH_PAIR_HOLD;   // k_solve_pair keeps the unrelaxed iterate in VGPRs
-#ifndef RH_PAIR_PB
-#define RH_PAIR_PB 2
-#endif
-constexpr int kPairPB = RH_PAIR_PB;   // bins per lane in phase A at 1024 threads
-#else
-constexpr int kGroupCases = 1;   // no grouped kernel in the shipped library: group_start is ignored
-#endif
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -233,48 +183,22 @@ extern "C" {
 
 const char* rh_last_error(void) { return g_err.c_str(); }
 
-int rh_version(void) { return 7; }
+int rh_version(void) { return 8; }
 
 // (rh_prof_read / rh_wgt_read of instrumented builds live in rh_solve_fast.hip, beside the counters)
 
 int rh_set_solver(rh_ctx* ctx, int which) {
   if (!ctx) return fail(RH_EINVAL, "rh_set_solver: null context");
-#ifdef RH_VARIANTS
-  if (which < 0 || which > 9 || which == 7)
-    return fail(RH_EINVAL,
-                "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 2 = ungrouped, 3 = k_solve_pair, "
-                "4 / 5 = ungrouped, k_solve_lds in one / two passes, 6 = auto with every axial row, "
-                "8 = auto with one phase-C sweep per bin, 9 = 6 and 8)", which);
-  ctx->no_group = which >= 2 && which < 6;
-  ctx->use_pair = which == 3 || (which == 0 && RH_PAIR_ON);
-  ctx->two_pass = which == 5 || (which != 4 && RH_TWO_PASS);
-#else
   if (which != 0 && which != 1 && which != 6 && which != 8 && which != 9)
     return fail(RH_EINVAL, "rh_set_solver: which=%d (0 = auto, 1 = general kernel, 6 = auto with every axial row, "
-                "8 = auto with one phase-C sweep per bin, 9 = 6 and 8; "
-                "the grouped, lane-pair and two-pass kernels are tools/ubench variant builds)", which);
-#endif
+                "8 = auto with one phase-C sweep per bin, 9 = 6 and 8)", which);
   ctx->force_general = which == 1;
   ctx->all_axial = which == 6 || which == 9;
   ctx->split_c = which == 8 || which == 9;
   return RH_OK;
 }
 
-int rh_group_cases(void) { return kGroupCases; }
-
 int rh_solve_noxi_max_bins(void) { return 2 * rh::kLT; }
-
-int rh_set_a0(rh_ctx* ctx, int on) {
-  if (!ctx) return fail(RH_EINVAL, "rh_set_a0: null context");
-  if (on != 0 && on != 1) return fail(RH_EINVAL, "rh_set_a0: on=%d (0 or 1)", on);
-#ifdef RH_VARIANTS
-  ctx->a0 = on != 0;
-#else
-  if (on) return fail(RH_EINVAL, "rh_set_a0: k_a0_sums is not in the shipped library (measured slower, DESIGN.md §5; "
-                                 "tools/build_variants.sh builds it)");
-#endif
-  return RH_OK;
-}
 
 int rh_set_qtf_waves(rh_ctx* ctx, int waves) {
   if (!ctx) return fail(RH_EINVAL, "rh_set_qtf_waves: null context");
@@ -286,18 +210,8 @@ int rh_set_qtf_waves(rh_ctx* ctx, int waves) {
 
 int rh_set_qtf_path(rh_ctx* ctx, int path) {
   if (!ctx) return fail(RH_EINVAL, "rh_set_qtf_path: null context");
-  if (path < 0 || path > 3)
-    return fail(RH_EINVAL, "rh_set_qtf_path: path=%d (0 = MFMA GEMMs when order == 1, 1 = per-pair kernel, "
-                           "2 = MFMA GEMMs with 32 x 32 tiles for a whole QTF, 3 = the GEMM coefficients and "
-                           "Kim & Yue as two launches)", path);
-#ifdef RH_VARIANTS
-  ctx->qtf_t32 = path == 2;
-  ctx->qtf_sep = path == 3;
-#else
-  if (path >= 2)
-    return fail(RH_EINVAL, "rh_set_qtf_path: path %d is not in the shipped library (measured slower, DESIGN.md §5; "
-                           "tools/build_variants.sh builds it)", path);
-#endif
+  if (path != 0 && path != 1)
+    return fail(RH_EINVAL, "rh_set_qtf_path: path=%d (0 = MFMA GEMMs when order == 1, 1 = per-pair kernel)", path);
   ctx->qtf_direct = path == 1;
   return RH_OK;
 }
@@ -497,48 +411,6 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
   a.o = *out;
   a.bmat_nn = nnmax;
   a.all_axial = ctx->all_axial ? 1 : 0;
-#ifdef RH_VARIANTS
-  // Grouped path (rh_solve_grp.hip): kGroupCases cases of one (design, heading) per workgroup.
-  // (It does not report the convergence margin: with out->margin the ungrouped kernels run.)
-  if (cases->group_start && cases->ngroup > 0 && !ctx->force_general && !ctx->no_group && !out->margin) {
-    if (cases->ngroup > cases->ncase) return fail(RH_EINVAL, "rh_solve_cases: ngroup=%d > ncase", cases->ngroup);
-    const int npass = (nw + rh::kGT - 1) / rh::kGT;
-    const size_t lsm = rh::solve_grp_smem(nnmax, nmmax, npass, kGroupCases);
-    if (lsm <= 160 * 1024) {
-      hipLaunchKernelGGL(rh::k_solve_grp<kGroupCases>, dim3(cases->ngroup), dim3(rh::kGT), lsm, s, a,
-                         cases->group_start, cases->ngroup);
-      return designs_used(ctx, s);
-    }
-  }
-  // Opt-in path (rh_solve_pair.hip, rh_set_solver(ctx, 3)): one bin per lane, lane-pair LU,
-  // 4 waves per SIMD.  Parity-green but slower than k_solve_lds on C2.
-  if (nw <= 1024 && !ctx->force_general && ctx->use_pair) {
-    const int lt = nw <= 256 ? 256 : nw <= 512 ? 512 : 1024;
-    const int pb = lt == 1024 ? kPairPB : 1;
-    const size_t lsm = rh::solve_pair_smem(nnmax, nmmax, lt, pb);
-    if (lsm <= kMaxLds) {
-      dim3 grid(cases->ncase), block(lt);
-      if (lt == 256) hipLaunchKernelGGL((rh::k_solve_pair<256, 1, kPairRA, kPairRC, kPairHold>), grid, block, lsm, s, a);
-      else if (lt == 512) hipLaunchKernelGGL((rh::k_solve_pair<512, 1, kPairRA, kPairRC, kPairHold>), grid, block, lsm, s, a);
-      else hipLaunchKernelGGL((rh::k_solve_pair<1024, kPairPB, kPairRA, kPairRC, kPairHold>), grid, block, lsm, s, a);
-      return designs_used(ctx, s);
-    }
-  }
-#endif
-  // Cases that start from XiStart: phase A of iteration 0 for the whole batch as one GEMM
-  // launch (rh_a0.hip), its sums in each case's Xi_last block (k_solve_lds reads them first).
-  auto prep_a0 = [&]() -> int {
-#ifdef RH_VARIANTS
-    if (!ctx->a0 || cases->first_iter != 0 || cases->Xi_init || !rh::a0_fits(nw, nnmax) ||
-        rh::kA0StaticLds + rh::a0_smem(nnmax, nmmax) > kMaxLds)
-      return RH_OK;
-    dim3 g((cases->ncase + rh::kA0Cases - 1) / rh::kA0Cases, (rh::a0_chunks(nw) + rh::kA0Cpb - 1) / rh::kA0Cpb);
-    hipLaunchKernelGGL(rh::k_a0_sums, g, dim3(rh::kA0Threads), rh::a0_smem(nnmax, nmmax), s, a);
-    RH_HIP(hipGetLastError());
-    a.a0 = 1;
-#endif
-    return RH_OK;
-  };
   // Fast path (rh_solve.hip): XiLast in LDS, 512 threads per case (256 for nw <= 256), nw <= 1024.
   if (nw <= 2 * rh::kLT && !ctx->force_general) {
     // nw <= 256 on 128 threads x 2 bins (x 1 bin for nw <= 128), B_drag summed without the
@@ -550,7 +422,6 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
       const int nb128 = nw <= rh::kLT / 4 ? 1 : 2;
       const size_t lsm128 = rh::solve_lds_smem(nnmax, nmmax, nb128, rh::kLT / 4, true);
       if (lsm128 <= kMaxLds) {
-        if (int r = prep_a0()) return r;
         dim3 grid(cases->ncase), block(rh::kLT / 4);
         RH_HIP(rh::launch_solve_fast(nb128 == 1 ? rh::kSolve1x128 : rh::kSolve2x128, grid, block, lsm128, s, a));
         return designs_used(ctx, s);
@@ -560,27 +431,11 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
     const int lt = nw <= rh::kLT / 2 ? rh::kLT / 2 : rh::kLT;   // nw <= 256: 256 threads, two cases per CU
     const size_t lsm = rh::solve_lds_smem(nnmax, nmmax, nb, lt);
     if (lsm <= 160 * 1024) {
-      if (int r = prep_a0()) return r;
       dim3 grid(cases->ncase), block(lt);
       // (two bins: both in one phase-C sweep, which parks bin 1's excitation in the case's Xi, Xi_last
       // or F_wave block; one sweep per bin on request, or for a call that has none of the three)
       const bool split_c = ctx->split_c || !(out->Xi || out->Xi_last || out->F_wave);
       const int kern = lt < rh::kLT ? rh::kSolve1x256 : nb == 1 ? rh::kSolve1x512 : split_c ? rh::kSolve2x512Split : rh::kSolve2x512;
-#ifdef RH_VARIANTS
-      // Two passes when the batch needs more than one round of workgroups (measured slower on
-      // C2: 0.895 vs 0.828 ms).  Pass 1 runs every case up to its last possible
-      // iteration, pass 2 finishes the cases that need it from the parked iterate.
-      const int nloop = cases->nIter + 1;
-      if (ctx->two_pass && nloop - 1 > cases->first_iter) {
-        int per_cu = 0;
-        RH_HIP(rh::occupancy_solve_fast(kern, &per_cu, lt, lsm));
-        if (cases->ncase > per_cu * ctx->ncu) {
-          a.stop_iter = nloop - 1;
-          RH_HIP(rh::launch_solve_fast(kern, grid, block, lsm, s, a));
-          a.resume = 1;
-        }
-      }
-#endif
       RH_HIP(rh::launch_solve_fast(kern, grid, block, lsm, s, a));
       return designs_used(ctx, s);
     }
@@ -590,7 +445,6 @@ int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_
   if (nw <= 4 * rh::kLT && !ctx->force_general) {
     const size_t lsm = rh::solve_lds_smem(nnmax, nmmax, 2, rh::kLT, false, 2);
     if (lsm <= kMaxLds) {
-      if (int r = prep_a0()) return r;
       hipLaunchKernelGGL((rh::k_solve_lds<2, rh::kLT, false, 2>), dim3(cases->ncase), dim3(rh::kLT), lsm, s, a);
       return designs_used(ctx, s);
     }
@@ -961,12 +815,7 @@ static int qtf_launch(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double*
     // the tables), then the pair tiles: bilinear + potential GEMMs plus the Kim & Yue sums, and
     // the Hermitian fill (rh_qtf_mfma.hip)
     const int bx0 = 16 * R0 / 64, nbx = blocks > 0 ? (16 * R1 + 63) / 64 - bx0 : 0;
-#ifdef RH_VARIANTS
-    const bool sep = ctx->qtf_sep, t32 = ctx->qtf_t32;
-#else
-    constexpr bool sep = false, t32 = false;
-#endif
-    if (blocks > 0 && !sep) {
+    if (blocks > 0) {
       // the Kim & Yue tiles and the GEMM coefficient blocks in one launch.  A call with few
       // tiles (a rank's share of a sharded QTF) gives each tile a workgroup and each part of a
       // member's rows a wave (S = kKayP); a whole QTF two tiles per workgroup (S = 1).  The same
@@ -982,25 +831,7 @@ static int qtf_launch(rh_ctx* ctx, const rh_qtf_design* q, int nw, const double*
         hipLaunchKernelGGL(rh::k_qtf_lk<1>, dim3(nkb + nbx * nly), dim3(rh::kLkThreads), 0, s, *q, wk, M66, t0, blocks,
                            nkb, bx0, nbx);
       RH_HIP(hipGetLastError());
-    } else {
-#ifdef RH_VARIANTS
-      hipLaunchKernelGGL(rh::k_qtf_lcoef, dim3(nb, 18 + q->nq + q->nmq), dim3(512), 0, s, *q, wk, M66);
-      RH_HIP(hipGetLastError());
-      if (blocks > 0) {
-        hipLaunchKernelGGL(rh::k_qtf_kay, dim3(blocks), dim3(rh::kKayThreads), 0, s, *q, wk, t0);
-        RH_HIP(hipGetLastError());
-      }
-#endif
-    }
-    if (blocks > 0) {
-      if (nrank == 1 && mirror && t32) {   // variant builds, a whole QTF: 32 x 32 pair tiles
-#ifdef RH_VARIANTS
-        const int nt32 = (nt + 1) / 2;
-        hipLaunchKernelGGL(rh::k_qtf_gemm32, dim3(nt32 * (nt32 + 1)), dim3(384), 0, s, *q, wk, qtf);
-#endif
-      } else {
-        hipLaunchKernelGGL(rh::k_qtf_gemm, dim3(6 / rh::kGD * blocks), dim3(rh::kGThreads), 0, s, *q, wk, qtf, t0, mirror);
-      }
+      hipLaunchKernelGGL(rh::k_qtf_gemm, dim3(6 / rh::kGD * blocks), dim3(rh::kGThreads), 0, s, *q, wk, qtf, t0, mirror);
       RH_HIP(hipGetLastError());
     }
     return RH_OK;

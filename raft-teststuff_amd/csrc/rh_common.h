@@ -202,14 +202,6 @@ struct CaseArgs {
   const DevDesign* designs;
   rh_cases c;
   rh_solve_out o;
-  // two-pass launch of k_solve_lds (rh_solve_cases): pass 1 stops a case before iteration
-  // stop_iter, parks its relaxed iterate in o.Xi_last and marks it kCaseStopped; pass 2
-  // (resume = 1) continues only those cases from there.  The default runs one pass.
-  int stop_iter = 1 << 30;
-  int resume = 0;
-  // 1: k_a0_sums has written every case's iteration-0 phase-A sums to its Xi_last block
-  // (rh_a0.hip); k_solve_lds skips phase A of iteration 0 and reads them in phase B
-  int a0 = 0;
   // node stride of the Bmat output ([ncase][bmat_nn][9]): the largest nn of the call's designs,
   // so designs with different node counts share one output array (rh_solve_cases sets it)
   int bmat_nn = 0;
@@ -217,6 +209,5 @@ struct CaseArgs {
   // wave-table row, as a design with Cd_q != 0 on every member does (cross-checks of the skip)
   int all_axial = 0;
 };
-constexpr int kCaseStopped = 9;   // internal status between the two passes (never returned)
 
 }  // namespace rh

@@ -777,7 +777,7 @@ __device__ __forceinline__ void lcoef_block(const rh_qtf_design& q, const QtfWor
 // registers, not a double buffer: k-step s + j is consumed from slot j, which is then refilled with
 // k-step s + PF + j, so PF steps stay in flight with half the operand registers (the kernel fits 128
 // VGPRs: four waves per SIMD).  One MFMA chain per product, every accumulator's k-steps in order (the
-// k-step order of k_qtf_gemm32: sharded == whole, bit for bit; two accumulator sets break that).
+// k-step order in which sharded == whole, bit for bit; two accumulator sets break that).
 __device__ __forceinline__ void cgemm_ring2(const rh_c128* __restrict__ A1, const rh_c128* __restrict__ B1, int n1,
                                             const rh_c128* __restrict__ A2, const rh_c128* __restrict__ B2, int n2,
                                             size_t step, d4& p1, d4& p2, d4& p3, d4& c1, d4& c2, d4& c3) {
@@ -858,9 +858,8 @@ __device__ __forceinline__ void qtf_pot_scalars(double w1, double k1, double t1,
   }
 }
 
-// The final sum of a pair entry, shared by k_qtf_gemm and k_qtf_gemm32 and written out with
-// contraction off, so that both kernels (the row-sharded and the whole QTF) produce the same
-// bits: (bilinear part + second half) + (alpha+ P+ + alpha- P-) + Kim & Yue.
+// The final sum of a pair entry, written out with contraction off, so that the row-sharded and
+// the whole QTF produce the same bits: (bilinear part + second half) + (alpha+ P+ + alpha- P-) + Kim & Yue.
 __device__ __forceinline__ cd qtf_pair_sum(double mre, double mim, double hre, double him, double ppr, double ppi,
                                            double pmr, double pmi, double spr, double spi, double smr, double smi,
                                            double ksr, double ksi) {

@@ -18,9 +18,6 @@
 //     end drag, in short loops of their own after the node loops of phases A and C; elsewhere it
 //     would meet coefficients that are exact zeros.
 #include "rh_common.h"
-#ifdef RH_VARIANTS
-#include "../../tools/ubench/variants_src/rh_a0_common.h"   // k_a0_sums sums (rh_set_a0)
-#endif
 
 namespace rh {
 
@@ -349,15 +346,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
 #endif
   const int slot = xcd_remap(blockIdx.x, a.c.ncase);
   const int ic = a.c.order ? a.c.order[slot] : slot;
-#ifdef RH_VARIANTS
-  // two-pass launch (a tools/ubench variant, rh_abi.hip): pass 2 runs only the parked cases
-  const bool resume = a.resume != 0;
-  const int stop_iter = a.stop_iter;
-  if (resume && a.o.status[ic] != kCaseStopped) return;   // uniform
-#else
-  constexpr bool resume = false;
-  constexpr int stop_iter = 1 << 30;
-#endif
   const rh_design& d = a.designs[a.c.design[ic]].d;
   const int nw = d.nw, nn = d.nn, nm = d.nm;
   const unsigned nw16 = (unsigned)nw * 16u;
@@ -376,11 +364,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   // PSD / RAO / RMS sums formed in phase C, where it stores Xi (no read-back), by the 512-thread
   // kernels; the SER kernels (C4's fixed point: no response output) keep them in the epilogue
   constexpr bool kStatsC = !SER && NB > 1;
-#ifndef RH_VARIANTS
   constexpr bool kOv = !GX;                        // the vote deferred into the next phase A (below)
-#else
-  constexpr bool kOv = false;                      // (variants: the two-pass launch stops mid-loop)
-#endif
   auto wave_maxes = [&](const double* m) {         // max of the per-wave convergence-margin partials
     double mx = m[0];
     for (int w = 1; w < LW; ++w) mx = fmax(mx, m[w]);
@@ -444,30 +428,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   for (int e = tid; e < 6 * kGhost; e += LT) al[6 * nn + e] = 0.0;
   for (int e = tid; e < kGhost; e += LT) nt[nn + e] = 0.0;
   if (tid < 5) sflag[tid] = 0;
-  const int it0 = resume ? stop_iter : a.c.first_iter;
-  // Iteration 0's phase-A sums formed for the whole batch by k_a0_sums (rh_a0.hip): their
-  // chunk sums (in chunk order) take the place of wave 0's partials and the other waves' are 0,
-  // so phase B's wave-order sum returns them unchanged; phase A of that iteration is skipped.
-  // (Read before the prologue: with GX the same Xi_last block then receives XiLast.)
-#ifdef RH_VARIANTS
-  bool skip_a = a.a0 != 0 && it0 == 0;   // uniform
-#else
-  constexpr bool skip_a = false;         // k_a0_sums is a variant kernel (tools/ubench/variants_src/rh_a0.hip)
-#endif
-  if (skip_a) {
-#ifdef RH_VARIANTS
-    const double* a0s = a0_block(a, ic, nw);
-    const int nch = a0_chunks(nw);
-    for (int e = tid; e < nn * 3; e += LT) {
-      double s = 0;
-      for (int ch = 0; ch < nch; ++ch) s += a0s[(size_t)ch * 3 * nn + e];
-      red[e * LW] = s;
-#pragma unroll
-      for (int w = 1; w < LW; ++w) red[e * LW + w] = 0.0;
-    }
-    __syncthreads();
-#endif
-  }
+  const int it0 = a.c.first_iter;
 
   // Per-bin scalars live in LDS, not in registers: nothing per-thread stays live across the
   // phases, so the register-heavy solve of phase C does not push other values to scratch.
@@ -477,7 +438,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   {
     const int spec = a.c.spectrum[ic];
     const double Hs = a.c.Hs[ic], Tp = a.c.Tp[ic], gam = a.c.gamma[ic];
-    const rh_c128* XI0 = resume ? a.o.Xi_last + c6 : a.c.Xi_init ? a.c.Xi_init + c6 : nullptr;
+    const rh_c128* XI0 = a.c.Xi_init ? a.c.Xi_init + c6 : nullptr;
     // (the loads first, then the spectrum from LDS: a loop that both loads and evaluates the
     // spectrum's transcendentals keeps scratch stores beside its loads under the max-ilp scheduler)
 #pragma unroll
@@ -489,7 +450,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       for (int c = 0; c < 6; ++c) {
         const cd x0 = okb ? (XI0 ? ld(XI0 + c * nw + b) : mk(a.c.XiStart, 0.0)) : mk(0.0, 0.0);
         if constexpr (GX) {
-          if (okb && !resume) st(XL + c * nw + b, x0);
+          if (okb) st(XL + c * nw + b, x0);
         } else {
           xl[c * NWP + b] = x0;
         }
@@ -510,9 +471,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   const int nloop = a.c.nIter + 1;
   const double tol = a.c.tol;
   int status = RH_CASE_NOT_CONVERGED, iters = nloop;
-  // closest call of the convergence test (rh_solve_out.margin); pass 2 continues pass 1's
-  double margin = resume && a.o.margin ? a.o.margin[ic] : INFINITY;
-  const int itend = resume || stop_iter >= nloop ? nloop : stop_iter;
+  double margin = INFINITY;   // closest call of the convergence test (rh_solve_out.margin)
   __syncthreads();
   PROF_T(tp1);
   PROF_ADD(0, tp1 - tp0);
@@ -792,6 +751,14 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
   };
 
   const double hdw = 0.5 / d.dw;   // psd = |x|^2 hdw and rao = x (1 / zeta): multiplies, not 36 divisions per thread
+  // What the removed two-pass launch left in the device code: its default stop
+  // iteration was the constant 1 << 30, which the compiler cannot prove >= nloop, so the shipped
+  // kernels have always carried this cap and the park-and-stop block of the epilogue below.  No
+  // call reaches them (nIter < 2^30), but without them every k_solve_lds instantiation gets
+  // another register allocation (254 instead of 255 VGPRs in <2, 512>, which tests/test_isa_joint_c.py
+  // pins): they go in a change with its own timing.
+  constexpr int kIterCap = 1 << 30;
+  const int itend = kIterCap >= nloop ? nloop : kIterCap;
   for (int it = it0; it < itend; ++it) {
     PROF_T(ta0);
     PROF_ADD(7, 1);
@@ -913,12 +880,11 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       static_assert(kRingA == 4 || kRingA == 3, "phase A reduces a round of 4 nodes (tbfly8) or single nodes at depth 3");
       constexpr bool kQuad = kRingA == 4;
       constexpr int kAx = kQuad ? 4 : 3;   // axial nodes per butterfly
-      const int nA = skip_a ? 0 : nn;   // no node steps when iteration 0's sums came from k_a0_sums
       // The first kAx axial rows are requested before the ring's, so they arrive behind the
       // transverse loop; a design with more axial nodes waits once per further kAx of them.
       cd KQ[kAx][NB];
 #pragma unroll
-      for (int r = 0; r < kAx; ++r) load_axial(KQ[r], nA > 0 ? r : nn);
+      for (int r = 0; r < kAx; ++r) load_axial(KQ[r], nn > 0 ? r : nn);
       // The ring slot of node n is refilled with node n + kRingA.
       cd K[kRingA][2][NB];
 #pragma unroll
@@ -935,7 +901,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       // are reduced like any other's and written nowhere.  node n's t is read a node ahead.
       double tn = nt[0];
 #pragma unroll 1
-      for (int n = 0; n < nA; n += kRingA) {
+      for (int n = 0; n < nn; n += kRingA) {
 #pragma unroll
         for (int r = 0; r < kRingA; ++r) {
           const int nr = n + r;
@@ -958,7 +924,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
             u8[2 * r + 1] = s2;
             if (r == kRingA - 1) {   // (folded by the unrolling)
               const double tot = tbfly8(u8, bl);
-              if (bl.vi8 >= 0 && n + (bl.vi8 >> 1) < nA) {
+              if (bl.vi8 >= 0 && n + (bl.vi8 >> 1) < nn) {
                 double& rr = red[((n + (bl.vi8 >> 1)) * 3 + 1 + (bl.vi8 & 1)) * LW + wv_s];
                 rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
               }
@@ -966,7 +932,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
           } else {
             const int ln = lane_here();
             const double tot = tbfly3(s1, s2, 0.0, ln);
-            if (ln < 3 && tbfly3_index(ln) < 2 && nr < nA) {
+            if (ln < 3 && tbfly3_index(ln) < 2 && nr < nn) {
               double& rr = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
               rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
             }
@@ -975,7 +941,7 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
       }
       // the axial nodes, kAx per butterfly, each with the Bq of its member
       int ma = 0;
-      for (int k0 = 0; k0 < nA; k0 += kAx) {
+      for (int k0 = 0; k0 < nn; k0 += kAx) {
         if (ax_node(k0) < 0) break;   // uniform: the end of the list
         double q[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -1014,9 +980,6 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         }
       }
     }
-#ifdef RH_VARIANTS
-    skip_a = false;
-#endif
     __syncthreads();
     if constexpr (kOv) {
       // the deferred vote of iteration it - 1 (every wave finished its phase C before this
@@ -1469,18 +1432,16 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
     }
   }
 
-  if (status == RH_CASE_NOT_CONVERGED && itend < nloop) {
-    // pass 1 stops here: park the relaxed iterate (the next iteration's XiLast) and the margin
-    // so far; pass 2 continues the case from iteration itend with the same bits
+  if (status == RH_CASE_NOT_CONVERGED && itend < nloop) {   // unreachable: see kIterCap
 #pragma unroll 1
-    for (int j = 0; j < NB && !GX; ++j) {   // (GX: XiLast is already in Xi_last)
+    for (int j = 0; j < NB && !GX; ++j) {
       const int b = tid + LT * j;
       if (b >= nw) continue;
 #pragma unroll 1
       for (int c = 0; c < 6; ++c) st(a.o.Xi_last + c6 + c * nw + b, xl[c * NWP + b]);
     }
     if (tid == 0) {
-      a.o.status[ic] = kCaseStopped;
+      a.o.status[ic] = 9;
       if (a.o.margin) a.o.margin[ic] = margin;
     }
     return;

@@ -27,16 +27,6 @@ hipError_t launch_solve_fast(int which, dim3 grid, dim3 block, size_t lsm, hipSt
   return hipGetLastError();
 }
 
-hipError_t occupancy_solve_fast(int which, int* per_cu, int threads, size_t lsm) {
-  switch (which) {
-    case kSolve1x256: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<1, kLT / 2>, threads, lsm);
-    case kSolve1x512: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<1>, threads, lsm);
-    case kSolve2x512: return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds<2>, threads, lsm);
-    case kSolve2x512Split: return occupancy_solve_split(per_cu, threads, lsm);
-    default: return hipErrorInvalidValue;
-  }
-}
-
 }  // namespace rh
 
 // Diagnostics of instrumented builds (tools/ubench/time_solve.py): they read this unit's counters,

@@ -15,9 +15,7 @@ enum SolveFast {
 };
 
 hipError_t launch_solve_fast(int which, dim3 grid, dim3 block, size_t lsm, hipStream_t s, const CaseArgs& a);
-hipError_t occupancy_solve_fast(int which, int* per_cu, int threads, size_t lsm);
-// kSolve2x512Split (rh_solve_split.hip, a translation unit of its own), reached through the two above
+// kSolve2x512Split (rh_solve_split.hip, a translation unit of its own), reached through the one above
 hipError_t launch_solve_split(dim3 grid, dim3 block, size_t lsm, hipStream_t s, const CaseArgs& a);
-hipError_t occupancy_solve_split(int* per_cu, int threads, size_t lsm);
 
 }  // namespace rh

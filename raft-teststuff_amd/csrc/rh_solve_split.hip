@@ -22,8 +22,4 @@ hipError_t launch_solve_split(dim3 grid, dim3 block, size_t lsm, hipStream_t s, 
   return hipGetLastError();
 }
 
-hipError_t occupancy_solve_split(int* per_cu, int threads, size_t lsm) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_solve_lds_split<2>, threads, lsm);
-}
-
 }  // namespace rh

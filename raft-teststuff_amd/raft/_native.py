@@ -43,7 +43,7 @@ class RhCases(ctypes.Structure):
     _fields_ = [("ncase", ctypes.c_int), ("design", _p), ("head", _p), ("spectrum", _p),
                 ("Hs", _p), ("Tp", _p), ("gamma", _p), ("nIter", ctypes.c_int),
                 ("XiStart", ctypes.c_double), ("tol", ctypes.c_double), ("fext", _p), ("order", _p),
-                ("Xi_init", _p), ("first_iter", ctypes.c_int), ("group_start", _p), ("ngroup", ctypes.c_int)]
+                ("Xi_init", _p), ("first_iter", ctypes.c_int)]
 
 
 class RhSolveOut(ctypes.Structure):
@@ -195,7 +195,6 @@ def lib():
                 "rh_qtf_keeps_incident": [_p, ctypes.POINTER(RhQtfDesign)],
                 "rh_qtf_hermitian_fill": [_p, ctypes.c_int, _p, _p],
                 "rh_set_solver": [_p, ctypes.c_int],
-                "rh_set_a0": [_p, ctypes.c_int],
                 "rh_set_qtf_waves": [_p, ctypes.c_int],
                 "rh_set_qtf_path": [_p, ctypes.c_int],
                 "rh_qtf_hankel": [_p, ctypes.c_int, _p, ctypes.c_int, _p, _p, _p],
@@ -218,8 +217,6 @@ def lib():
             L.rh_prep_imat.argtypes = [_p, ctypes.c_int, _p]
             L.rh_prep_imat.restype = ctypes.c_longlong
             L.rh_version.restype = ctypes.c_int
-            L.rh_group_cases.argtypes = []
-            L.rh_group_cases.restype = ctypes.c_int
             L.rh_solve_noxi_max_bins.argtypes = []
             L.rh_solve_noxi_max_bins.restype = ctypes.c_int
             L.rh_qtf_workspace_bytes.argtypes = [ctypes.POINTER(RhQtfDesign)]

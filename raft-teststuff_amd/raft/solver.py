@@ -7,7 +7,6 @@ case, one workgroup per case; cases are launched sorted by (design, heading) so 
 blocks an XCD receives stream the same wave tables out of its L2.
 """
 import ctypes
-import os
 
 import numpy as np
 
@@ -112,7 +111,6 @@ def solve_batch(designs, cases, nIter, XiStart=0.0, tol=0.01, want=("psd", "std"
     cs.fext = N.ptr(fext)
     cs.order = N.ptr(prep["order"])
     cs.Xi_init, cs.first_iter = N.ptr(Xi_init), int(first_iter)
-    cs.group_start, cs.ngroup = N.ptr(prep["group_start"]), int(prep["ngroup"])
     o = N.RhSolveOut()
     o.Xi, o.Xi_last, o.iters, o.status = N.ptr(out.get("Xi")), N.ptr(xl), N.ptr(out["iters"]), N.ptr(out["status"])
     for k in ["zeta", "B_drag", "Bmat", "psd", "std", "rao", "Z", "Xi_prev", "margin"]:
@@ -146,27 +144,14 @@ def prepare_batch(designs, cases, tables_stream=None):
             d = designs[int(di)]
             sel = np.nonzero(cases.design_idx == di)[0]
             head[sel] = d.ensure_headings(cases.heading[sel] * DEG2RAD)
-    # Lock-step groups (k_solve_grp) exist only in tools/ubench variant builds of the library
-    # (rh_group_cases() > 1 there) and are opt-in even then: RAFT_GROUP_WIDTH=2.  Measured on
-    # the C2 batch they halve the wave-table stream but not the time per case.
-    width = min(N.lib().rh_group_cases(), int(os.environ.get("RAFT_GROUP_WIDTH", "1") or 1))
-    if width > 1:
-        # design-major, then heading; within a (design, heading) run by sea state, so that
-        # the cases solved in lock-step by one workgroup tend to need the same iterations
-        order = np.lexsort((cases.Tp, cases.Hs, head, cases.design_idx)).astype(np.int32)
-        gstart = case_groups(cases.design_idx[order], head[order], width)
-    else:
-        order = balanced_order(cases, head)
-        gstart = None
+    order = balanced_order(cases, head)
     # two uploads (the int and the float case columns), each column a view
     n = cases.n
     ints = torch.from_numpy(np.concatenate([cases.design_idx, np.asarray(head, dtype=np.int32), cases.spectrum,
                                             order]).astype(np.int32, copy=False)).to(dev)
     flts = torch.from_numpy(np.concatenate([cases.Hs, cases.Tp, cases.gamma]).astype(np.float64, copy=False)).to(dev)
     return dict(design=ints[:n], head=ints[n:2 * n], spectrum=ints[2 * n:3 * n], order=ints[3 * n:4 * n],
-                Hs=flts[:n], Tp=flts[n:2 * n], gamma=flts[2 * n:3 * n], head_host=head,
-                group_start=None if gstart is None else torch.tensor(gstart, dtype=torch.int32, device=dev),
-                ngroup=0 if gstart is None else len(gstart) - 1)
+                Hs=flts[:n], Tp=flts[n:2 * n], gamma=flts[2 * n:3 * n], head_host=head)
 
 
 def balanced_order(cases, head, nxcd=8):
@@ -206,8 +191,9 @@ def balanced_order(cases, head, nxcd=8):
 
 
 def case_groups(design, head, width):
-    """Offsets of the lock-step groups of rh_cases.group_start: consecutive (already sorted)
-    cases with equal design and heading index, at most `width` per group."""
+    """Offsets of groups of consecutive (already sorted) cases with equal design and heading
+    index, at most `width` per group.  (The host side of the removed lock-step kernel; no launch
+    uses it.)"""
     n = len(design)
     if n == 0:
         return np.zeros(1, dtype=np.int32)

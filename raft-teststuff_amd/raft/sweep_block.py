@@ -67,7 +67,6 @@ def prepare_block(P, designs, cases, device, compute):
     columns.  Returns (BlockDesigns, the prepared case columns of solver.prepare_batch), or None
     when the block needs the per-design path (tables not pinned, MacCamy-Fuchs inertia tables,
     or a design without cases)."""
-    import os
     from .prep import _torch
     from .solver import balanced_order
     if getattr(P, "pinned", None) is None or P.imat or cases.n == 0 or len(designs) != len(P.info):
@@ -75,8 +74,6 @@ def prepare_block(P, designs, cases, device, compute):
     if any(get_from_dict((d or {}).get("platform") or {}, "potSecOrder", dtype=int, default=0) > 0
            for d in {id(d): d for d in designs}.values()):
         return None
-    if int(os.environ.get("RAFT_GROUP_WIDTH", "1") or 1) > 1 and N.lib().rh_group_cases() > 1:
-        return None                                        # lock-step groups: solver.prepare_batch
     torch = _torch()
     dev = torch.device("cuda", device)
     info = P.info
@@ -137,7 +134,7 @@ def prepare_block(P, designs, cases, device, compute):
                                          ctypes.c_void_p(compute.cuda_stream)), "rh_wave_tables_batch")
     prep = dict(design=ints[:ncase], head=ints[ncase:2 * ncase], spectrum=ints[2 * ncase:3 * ncase],
                 order=ints[3 * ncase:4 * ncase], Hs=flts[:ncase], Tp=flts[ncase:2 * ncase], gamma=flts[2 * ncase:],
-                head_host=head, group_start=None, ngroup=0)
+                head_host=head)
     st0 = designs[0].get("settings", {})
     blk = BlockDesigns(torch, dev, device, arr, nd, nw, int(nn.max()), get_from_dict(st0, "nIter", default=15, dtype=int),
                        get_from_dict(st0, "XiStart", default=0.1, dtype=float), (flat, K, Fi, beta_t, rec))

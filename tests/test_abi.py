@@ -39,13 +39,13 @@ def test_library_exports_every_declared_symbol(libpath):
     exported = set(re.findall(r"\sT\s(rh_\w+)$", out, flags=re.M))
     missing = [f for f in declared_functions() if f not in exported]
     assert not missing, missing
+    assert "rh_set_a0" not in exported and "rh_group_cases" not in exported   # removed in ABI version 8
 
 
 def test_library_loads_and_binds(libpath):
     from raft import _native as N
     L = N.lib()
-    assert L.rh_version() == 7
-    assert L.rh_group_cases() >= 1
+    assert L.rh_version() == 8
     # the tuning knobs live on a context (no mutable process globals);
     # without a GPU there is no context, and a null one is rejected
     assert L.rh_set_solver(None, 0) == N.RH_EINVAL
@@ -83,6 +83,10 @@ def test_struct_layout_matches_header():
     assert fields("rh_cases") == [f[0] for f in N.RhCases._fields_]
     assert fields("rh_solve_out") == [f[0] for f in N.RhSolveOut._fields_]
     assert fields("rh_qtf_design") == [f[0] for f in N.RhQtfDesign._fields_]
+    assert fields("rh_bem_design") == [f[0] for f in N.RhBemDesign._fields_]
+    assert fields("rh_moor_system") == [f[0] for f in N.RhMoorSystem._fields_]
+    assert fields("rh_moor_array_system") == [f[0] for f in N.RhMoorArraySystem._fields_]
+    assert fields("rh_rotor") == [f[0] for f in N.RhRotor._fields_]
 
 
 def test_product_fails_loudly_without_gpu():

@@ -342,7 +342,7 @@ def test_abi_exports_the_new_calls():
     for sym in ["rh_moor_array_eval", "rh_array_statics_solve", "rh_array_solve_stats_ext"]:
         assert f" T {sym}\n" in out, sym
     L = N.lib()
-    assert L.rh_version() == 7
+    assert L.rh_version() == 8
     null = [None] * 12
     assert L.rh_moor_array_eval(None, None, None, 1, 1, *null[:11]) == N.RH_EINVAL
     assert b"null context" in L.rh_last_error()

@@ -359,7 +359,7 @@ def test_abi_exports_the_two_calls():
     for sym in ["rh_moor_eval", "rh_statics_solve"]:
         assert f" T {sym}\n" in out, sym
     L = N.lib()
-    assert L.rh_version() == 7
+    assert L.rh_version() == 8
     null = [None] * 12
     assert L.rh_moor_eval(None, None, None, 1, 1, *null[:9]) == N.RH_EINVAL
     assert b"null context" in L.rh_last_error()

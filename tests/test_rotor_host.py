@@ -282,7 +282,7 @@ def test_abi_exports_rotor_loads():
     out = subprocess.run(["nm", "-D", "--defined-only", g.LIB], capture_output=True, text=True, check=True).stdout
     assert " T rh_rotor_loads\n" in out
     L = N.lib()
-    assert L.rh_version() == 7
+    assert L.rh_version() == 8
     null = [None] * 7
     assert L.rh_rotor_loads(None, None, None, 1, 1, *null) == N.RH_EINVAL
     assert b"null context" in L.rh_last_error()

@@ -1,6 +1,7 @@
 // Stand-alone check of the batched entry points' argument errors, for a sanitizer run on the CPU:
 // rh_solve_cases, rh_wave_excitation, rh_heading_response and rh_array_solve_stats with no designs, with
-// null tables and with designs on different frequency grids must each return RH_EINVAL with a message.
+// null tables and with designs on different frequency grids, and rh_set_solver / rh_set_qtf_path with the
+// values of the removed variant kernels, must each return RH_EINVAL with a message.
 // These errors return before the context is read and before any HIP call, so the program needs no GPU:
 // the context is an opaque non-null pointer to one byte, which a sanitizer would see any access beyond.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
@@ -79,6 +80,15 @@ int main() {
                 rh_array_solve_stats(ctx, &no_w, 1, 1, 1, ii, dd, nullptr, cc, 0.0, nullptr, nullptr, nullptr));
   expect_einval("rh_array_solve_stats, mismatched nw",
                 rh_array_solve_stats(ctx, mixed, 2, 1, 1, ii, dd, nullptr, cc, 0.0, nullptr, nullptr, nullptr));
+
+  // the selectors of the removed variant kernels (refused before the context is written)
+  for (int which = 2; which <= 5; ++which) {
+    char what[32];
+    std::snprintf(what, sizeof what, "rh_set_solver, which = %d", which);
+    expect_einval(what, rh_set_solver(ctx, which));
+  }
+  expect_einval("rh_set_qtf_path, path = 2", rh_set_qtf_path(ctx, 2));
+  expect_einval("rh_set_qtf_path, path = 3", rh_set_qtf_path(ctx, 3));
 
   std::printf("%s\n", g_bad ? "FAILED" : "all argument errors returned RH_EINVAL with a message");
   return g_bad ? 1 : 0;

@@ -38,9 +38,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as G  # noqa: E402  (the build's translation units and their flags)
-# Every kernel of the shipped library is on some default dispatch path of rh_abi.hip (the opt-in
-# kernels measured slower were moved out into tools/ubench/variants_src, built only with
-# -DRH_VARIANTS), so every kernel is held to the streaming-loop rule.  The one exception is the
+# Every kernel of the library is on some default dispatch path of rh_abi.hip (the opt-in
+# kernels measured slower were removed), so every kernel is held to the streaming-loop rule.  The one exception is the
 # general case solve k_solve_cases<NB>, the default for nw > 1024 or node tables beyond the LDS:
 # a measured path whose current counts are a ratchet, so a change can only lower
 # them.  No other kernel can get a ratchet: an entry here must name a k_solve_cases instantiation.

@@ -1,7 +1,7 @@
 # rh_prep_designs with and without its kept worker threads (round 6), alternating on one box:
 # tools/ubench/c5_rank.py at N = 1 (16 host threads) and as rank 0 of 8 (2 threads).
 #   lib_nopool: the library before the pool (threads spawned and joined per call), built by
-#   VARIANT_BASE="" tools/build_variants.sh nopool "" from that source; main: the tree's library.
+#   tools/build_variants.sh nopool "" from that source; main: the tree's library.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-c5pool}; mkdir -p $O; cd $R
 for rep in 1 2 3; do
   for v in nopool main; do

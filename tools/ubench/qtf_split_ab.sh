@@ -2,7 +2,7 @@
 # split), one wave per part of a member's rows (kay2: always), and the shipped rule (main:
 # split up to ncu / 2 tiles per call), alternating on one box.  tools/ubench/time_qtf.py ranks
 # N: rank r of N (rh_qtf_slender_rows) and the whole QTF, microseconds per call.
-#   VARIANT_BASE="" tools/build_variants.sh kay1 "-DRH_KAY_SPLIT_MAX_TILES(n)=0" kay2 "-DRH_KAY_SPLIT_MAX_TILES(n)=100000"
+#   tools/build_variants.sh kay1 "-DRH_KAY_SPLIT_MAX_TILES(n)=0" kay2 "-DRH_KAY_SPLIT_MAX_TILES(n)=100000"
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-qtfsplit}; mkdir -p $O; cd $R
 for rep in 1 2; do
   for v in kay1 kay2 main; do

@@ -1,5 +1,6 @@
 """Time the C2 bench batch (512 cases, nw=1000) with the library named by RAFTHIP_LIB;
-prints ms per launch, mean iterations and ms per executed iteration."""
+prints ms per launch, mean iterations and ms per executed iteration, and with a -DRH_PROF library
+(tools/ubench/variants.py prof) the phase cycle counters per workgroup-iteration of wave 0."""
 import os
 import sys
 import time
@@ -37,15 +38,15 @@ def main(tag):
     L = N.lib()
     if hasattr(L, "rh_prof_read"):
         import ctypes
-        buf = (ctypes.c_ulonglong * 8)()
+        buf = (ctypes.c_ulonglong * 12)()   # rh_prof_read writes 12
         L.rh_prof_read(buf, 1)
         res = solve_batch([dd], cs, m.nIter, m.XiStart, 0.01, want=("psd", "std", "zeta", "rao"), prepared=prep)
         torch.cuda.synchronize()
         L.rh_prof_read(buf, 1)
         v = list(buf)
         nwg, nit = 512, max(v[7], 1)
-        names = ["prologue/WG", "A/iter", "B/iter", "C-exc/iter", "C-solve/iter", "flags/iter", "epilogue/WG"]
-        per = [v[0] / nwg, v[1] / nit, v[2] / nit, v[3] / nit, v[4] / nit, v[5] / nit, v[6] / nwg]
+        names = ["prologue/WG", "A/iter", "B/iter", "C-exc/iter", "C-solve/iter", "(Z/iter", "LU/iter)", "flags/iter", "epilogue/WG"]
+        per = [v[0] / nwg, v[1] / nit, v[2] / nit, v[3] / nit, v[4] / nit, v[8] / nit, v[9] / nit, v[5] / nit, v[6] / nwg]
         print("  cycles (s_memtime, wave 0): " + "  ".join(f"{n}={x:,.0f}" for n, x in zip(names, per)), flush=True)
 
 

@@ -56,7 +56,7 @@ EDITS = {
 def build(name, edits, flags=()):
     """Copy the sources, apply the edits and build tools/ubench/var_<name>.so as the library itself is built."""
     tmp = tempfile.mkdtemp()
-    for rel in (REL_CSRC, "include", os.path.join("tools", "ubench", "variants_src")):   # (csrc includes the other two by relative path)
+    for rel in (REL_CSRC, "include"):   # (csrc includes the header by relative path)
         shutil.copytree(os.path.join(ROOT, rel), os.path.join(tmp, rel))
     for fname, a, b in edits:
         p = os.path.join(tmp, REL_CSRC, fname)
