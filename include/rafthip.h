@@ -420,6 +420,39 @@ typedef struct {
 int rh_rotor_loads(rh_ctx* ctx, const rh_rotor* rot, const rh_rotor* rot_dev, int nrot, int npoint, const int* rot_idx,
                    const double* op, double* loads, double* dloads, double* sec, int* status, rh_stream stream);
 
+/* ---- aero-servo added mass and damping of batched wind cases (csrc/rh_aero.h, rh_aero.hip) ----
+ * The device form of the per-bin part of Rotor.calcAero (aeroServoMod 1 and 2; raft/rotor.py) and of
+ * FOWT.calcTurbineConstants' move to the platform reference point, fed by rh_rotor_loads' device
+ * outputs: the per-bin M and B of every case, as prep.linear_matrices sums them.  The wind
+ * excitation and the Kaimal spectrum are not covered (the response solve does not read them).
+ * One row of the parameter table per (case, rotor) pair, formed on the host: */
+enum rh_aero_param_field {
+  RH_AP_MODE = 0,              /* aeroServoMod, 1.0 or 2.0 */
+  RH_AP_RQ = 1,                /* R_q, row-major (9) */
+  RH_AP_RHUB = 10,             /* r_hub_rel [m] (3) */
+  RH_AP_I_DRIVETRAIN = 13, RH_AP_NG, RH_AP_K_FLOAT,
+  RH_AP_KP_BETA, RH_AP_KI_BETA,  /* the pitch gains at the case's wind speed */
+  RH_AP_KP_TAU, RH_AP_KI_TAU,    /* the torque gains, zero where the pitch gain is not */
+  RH_AP_GYRO = 20,             /* I_drivetrain q Omega(wind speed) 2 pi / 60 (3) */
+  RH_AP_COUNT = 24             /* (one pad) */
+};
+#define RH_AERO_MAX_PAIRS 8 /* pairs (operating rotors) of one case */
+
+/* M [ncase][nw][36] and B [ncase][nw][36] (device, 16-byte aligned) of ncase cases and f_aero0
+ * [ncase][6], the mean aero load about the platform reference point summed over the case's rotors.
+ * w: device [nw].  pair_case: device [npair], the case row of each pair, non-decreasing, the pairs
+ * of a case in rotor order, at most RH_AERO_MAX_PAIRS of them; pair_case_host and pair_mode_host
+ * (aeroServoMod, 1 or 2; the table's RH_AP_MODE holds the same value): HOST [npair], validated here
+ * before the launch.  loads [npair][8] and dloads [npair][2][3]: device, as rh_rotor_loads writes
+ * them.  param: device [npair][RH_AP_COUNT].  M0, B0: the base design's matrices, device [36] or,
+ * with base_per_bin != 0, [nw][36].  Per bin: M = sum of the pairs' a(w) P + M0, B = (sum of the
+ * pairs' b(w) P + B0) + the alternator matrix of the summed gyroscopic vectors in B[3:, 3:]; a case
+ * row that no pair names gets M0 and B0 unchanged and zeros in f_aero0. */
+int rh_rotor_aero_mb(rh_ctx* ctx, int ncase, int npair, int nw, const double* w, const int* pair_case,
+                     const int* pair_case_host, const int* pair_mode_host, const double* loads, const double* dloads,
+                     const double* param, const double* M0, const double* B0, int base_per_bin, double* M, double* B,
+                     double* f_aero0, rh_stream stream);
+
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
  * (raft/raft_model.py:877-1013) including FOWT.calcHydroLinearization (raft/raft_fowt.py:

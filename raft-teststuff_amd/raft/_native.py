@@ -115,6 +115,11 @@ RS_COUNT = len(ROTOR_SECTION_FIELDS)
 ROTOR_MAX_SECTIONS, ROTOR_MAX_SECTORS, ROTOR_MAX_KNOTS = 64, 16, 128
 ROTOR_STATUS = {0: "ok", 1: "a blade section without a sign change of the BEM residual in any bracket",
                 2: "non-finite rotor load", 3: "rotor index out of range"}
+# parameter-row layout of rh_rotor_aero_mb (enum rh_aero_param_field) and its limit of pairs per case
+AP = {"MODE": 0, "RQ": 1, "RHUB": 10, "I_DRIVETRAIN": 13, "NG": 14, "K_FLOAT": 15, "KP_BETA": 16, "KI_BETA": 17,
+      "KP_TAU": 18, "KI_TAU": 19, "GYRO": 20}
+AP_COUNT = 24
+AERO_MAX_PAIRS = 8
 
 
 class NativeError(RuntimeError):
@@ -158,6 +163,8 @@ def lib():
                                            _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_rotor_loads": [_p, ctypes.POINTER(RhRotor), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p,
                                    _p],
+                "rh_rotor_aero_mb": [_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                     ctypes.c_int, _p, _p, _p, _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,

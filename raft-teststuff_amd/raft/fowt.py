@@ -305,23 +305,46 @@ class FOWT:
         setYaw's tilt and yaw misalignment at the FOWT's current pose).  Returns one entry per case:
         the `bem` argument of calcTurbineConstants, a list with a (loads, derivs) pair per rotor
         (None for a rotor that does not operate).  A non-zero status raises RuntimeError."""
-        from . import _native as N
-        from .rotor_device import DeviceRotor, bem_pair
-        if self._rotor_submerged:
-            raise NotImplementedError("underwater rotors (raft/raft_rotor.py) are outside the accelerated path")
-        pairs = [(ic, ir) for ic, case in enumerate(cases) for ir in range(self.nrotors) if self._rotor_operates(ir, case)]
+        from .rotor_device import bem_pair
+        pairs, rotors = self._rotor_pairs(cases)
         out = [[None] * self.nrotors for _ in cases]
         if not pairs:
             return out
+        dr = self._device_rotor(rotors, device)
+        op, idx = self._rotor_operating_points(pairs, rotors, cases)
+        res = dr.launch(idx, op, derivatives=True)
+        self._check_rotor_status(res, pairs)
+        L, D = res["loads"].cpu().numpy(), res["dloads"].cpu().numpy()
+        for n, (ic, ir) in enumerate(pairs):
+            out[ic][ir] = bem_pair(dr.flat[idx[n]].nr, L[n], D[n], op[n, 1])
+        return out
+
+    # the steps rotorLoadsBatch and aeroMBBatch share
+    def _rotor_pairs(self, cases):
+        """The (case, rotor) pairs that operate, case after case and in rotor order, and the rotors
+        among them.  Host only."""
+        if self._rotor_submerged:
+            raise NotImplementedError("underwater rotors (raft/raft_rotor.py) are outside the accelerated path")
+        pairs = [(ic, ir) for ic, case in enumerate(cases) for ir in range(self.nrotors) if self._rotor_operates(ir, case)]
         rotors = sorted({ir for _, ir in pairs})
         for ir in rotors:
             if not isinstance(self.rnaList[ir], Rotor):
                 raise NotImplementedError("rotor aerodynamics need the turbine's blade, airfoil, operating-point "
                                           "and control inputs (raft/raft_rotor.py:37-374)")
+        return pairs, rotors
+
+    def _device_rotor(self, rotors, device):
+        """The DeviceRotor of these rotors' blades (kept until a blade or the device changes)."""
+        from .rotor_device import DeviceRotor
         key = (device,) + tuple(id(self.rnaList[ir].ccblade) for ir in rotors)
         if getattr(self, "_rotor_dev", None) is None or self._rotor_dev[0] != key:
             self._rotor_dev = (key, DeviceRotor([self.rnaList[ir].ccblade for ir in rotors], device))   # refusals first
-        dr = self._rotor_dev[1]
+        return self._rotor_dev[1]
+
+    def _rotor_operating_points(self, pairs, rotors, cases, each=None):
+        """op [npair, 5] and the rotor index of every pair, each operating point formed as
+        Rotor.calcAero and runCCBlade form it.  each(n, rot, speed) is called for pair n with the
+        rotor at that case's yaw."""
         op = np.zeros([len(pairs), 5])
         idx = np.zeros(len(pairs), dtype=np.int32)
         for n, (ic, ir) in enumerate(pairs):
@@ -330,15 +353,52 @@ class FOWT:
             tilt, yaw = rot.inflow_angles(case)
             op[n] = (*rot.operating_point(speed), tilt, yaw)
             idx[n] = rotors.index(ir)
-        res = dr.launch(idx, op, derivatives=True)
+            if each is not None:
+                each(n, rot, speed)
+        return op, idx
+
+    @staticmethod
+    def _check_rotor_status(res, pairs, who="rotorLoadsBatch"):
+        """Reads back the status column of a rotor launch; a non-zero status raises RuntimeError."""
         status = res["status"].cpu().numpy()
         if np.any(status):
             n = int(np.flatnonzero(status)[0])
-            raise RuntimeError(f"rotorLoadsBatch: case {pairs[n][0]}, rotor {pairs[n][1]}: status {int(status[n])} "
+            raise RuntimeError(f"{who}: case {pairs[n][0]}, rotor {pairs[n][1]}: status {int(status[n])} "
                                f"({N.ROTOR_STATUS.get(int(status[n]), '?')})")
-        L, D = res["loads"].cpu().numpy(), res["dloads"].cpu().numpy()
-        for n, (ic, ir) in enumerate(pairs):
-            out[ic][ir] = bem_pair(dr.flat[idx[n]].nr, L[n], D[n], op[n, 1])
+
+    def aeroMBBatch(self, cases, base, device=0):
+        """The per-bin M and B of every case with its operating rotors' aero-servo added mass and
+        damping and gyroscopic damping, on the device: the (case, rotor) pairs and operating points
+        of rotorLoadsBatch, one rh_rotor_loads launch and, on the same stream and fed by its device
+        outputs, one rh_rotor_aero_mb launch (raft/rotor_device.py).  base: the DeviceDesign of the
+        aero-free design, whose M and B every case starts from (a case without an operating rotor
+        gets them unchanged).  Only the status column is read back; a non-zero status raises the
+        RuntimeError of rotorLoadsBatch.  Returns device tensors M [n, nw, 6, 6], B [n, nw, 6, 6]
+        and f_aero0 [n, 6] (the mean aero load about the platform reference point, summed over the
+        case's rotors), or None when no rotor operates in any case.  What Rotor.calcAero also
+        forms, the wind excitation f_aero and the Kaimal spectrum, is not computed, and the FOWT's
+        A_aero, B_aero, f_aero and B_gyro are left as they are.  Refused by name before any device
+        call: underwater rotors, what flatten_rotor refuses, and an aeroServoMod other than 1 or 2
+        on an operating rotor."""
+        from .rotor_device import aero_mode, aero_param_row
+        pairs, rotors = self._rotor_pairs(cases)
+        if not pairs:
+            return None
+        modes = {ir: aero_mode(self.rnaList[ir], ir) for ir in rotors}
+        counts = np.bincount([ic for ic, _ in pairs])
+        if counts.max() > N.AERO_MAX_PAIRS:
+            raise NotImplementedError(f"device aero-servo matrices: {counts.max()} operating rotors in one case "
+                                      f"(at most {N.AERO_MAX_PAIRS})")
+        dr = self._device_rotor(rotors, device)      # flatten_rotor's refusals, then the first device call
+        param = np.zeros([len(pairs), N.AP_COUNT])
+
+        def row(n, rot, speed):
+            param[n] = aero_param_row(rot, speed, modes[pairs[n][1]])
+        op, idx = self._rotor_operating_points(pairs, rotors, cases, each=row)
+        res = dr.launch(idx, op, derivatives=True)
+        out = dr.aero_mb(res, len(cases), [ic for ic, _ in pairs], [modes[ir] for _, ir in pairs], param, base.w,
+                         base.M, base.B)
+        self._check_rotor_status(res, pairs, "aeroMBBatch")
         return out
 
     def calcTurbineConstants(self, case, ptfm_pitch=0, bem=None):

@@ -765,7 +765,7 @@ class Model:
         return self.results
 
     def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
-                          pose_chunk=32, rotor_device=False):
+                          pose_chunk=32, rotor_device=False, aero_device=False):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -793,7 +793,22 @@ class Model:
         rotor_device=True takes the blade-element loads of every case with an operating rotor from one
         device launch (FOWT.rotorLoadsBatch) ahead of the per-case loop instead of one host CCBlade
         evaluation per case; a case whose rotor solve fails raises RuntimeError.  The default changes
-        nothing."""
+        nothing.
+        aero_device=True (single FOWT, statics=False) also forms every wind case's per-bin M and B on
+        the device (FOWT.aeroMBBatch: the rotor launch and one rh_rotor_aero_mb launch on the same
+        stream; it implies the device rotor solve): no per-case host arithmetic over bins and no
+        per-case upload, each such case's design a view of one row of two [n_wind, nw, 6, 6] tensors.
+        The result gains f_aero0 [n, 6], the mean aero load about the platform reference point (zeros
+        for a case without aero).  The wind excitation and the Kaimal spectrum are not computed (the
+        solve reads neither), and the FOWT's host attributes A_aero, B_aero, f_aero and B_gyro stay as
+        the aero-free design sets them: all zeros.  With statics=True and on an array it raises
+        NotImplementedError.  The default changes nothing."""
+        if aero_device and statics:
+            raise NotImplementedError("analyzeCasesBatch: aero_device=True with statics=True (the per-pose path "
+                                      "rebuilds a design per case; use rotor_device=True there)")
+        if aero_device and self.nFOWT != 1:
+            raise NotImplementedError("analyzeCasesBatch: aero_device=True on an array (analyzeArrayBatch without "
+                                      "statics does not evaluate rotors)")
         if statics:
             return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device)
         if self.nFOWT != 1:
@@ -816,6 +831,9 @@ class Model:
             res = solve_batch_2nd(views, [fowt], cs, self.nIter, self.XiStart, tol, want=want_fp)
             if multi:
                 self._extra_sea_states(res, views, cs.design_idx, seas, nws, want)
+            if aero_device:
+                import torch
+                res["f_aero0"] = torch.zeros([len(cases), 6], dtype=torch.float64, device=views[0].device)
             return res.host() if host else res
         # operating rotors: each such case gets its own per-bin M and B (its rotors' aero-servo
         # added mass and damping, FOWT.calcTurbineConstants) on the shared node and wave tables
@@ -826,11 +844,18 @@ class Model:
         base.ensure_headings(np.unique(np.asarray(hd, dtype=float)) * DEG2RAD)
         views, idx = [base], np.zeros(len(cases), dtype=np.int32)
         bems = {}
-        if rotor_device:
-            sel = [i for i in range(len(cases)) if aero[i]]
+        sel = [i for i in range(len(cases)) if aero[i]]
+        mb = None
+        if aero_device:      # every wind case's M and B from two launches; its CaseMB views a row of them
+            mb = fowt.aeroMBBatch([dict(cases[i]) for i in sel], base, self.device)
+            if mb is not None:
+                for row, i in enumerate(sel):
+                    views.append(CaseMB(base, mb["M"][row], mb["B"][row]))
+                    idx[i] = len(views) - 1
+        elif rotor_device:
             bems = dict(zip(sel, fowt.rotorLoadsBatch([dict(cases[i]) for i in sel], self.device)))
         for i, c in enumerate(cases):
-            if aero[i]:
+            if aero[i] and not aero_device:
                 fowt.calcTurbineConstants(dict(c), ptfm_pitch=0, bem=bems.get(i))
                 M, B, _, _ = linear_matrices(fowt)
                 f64 = dict(dtype=torch.float64, device=base.device)
@@ -840,6 +865,11 @@ class Model:
         res = solve_batch_2nd(views, [fowt] * len(views), cs, self.nIter, self.XiStart, tol, want=want_fp)
         if multi:
             self._extra_sea_states(res, views, idx, seas, nws, want)
+        if aero_device:
+            f0 = torch.zeros([len(cases), 6], dtype=torch.float64, device=base.device)
+            if mb is not None:
+                f0[torch.tensor(sel, dtype=torch.long, device=base.device)] = mb["f_aero0"]
+            res["f_aero0"] = f0
         return res.host() if host else res
 
     def _calc_bem_once(self):

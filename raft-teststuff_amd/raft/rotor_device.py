@@ -125,6 +125,35 @@ def bem_pair(nr, loads8, dloads6, Omega_rpm):
     return loads, derivs
 
 
+def aero_mode(rot, ir):
+    """aeroServoMod of an operating rotor as rh_rotor_aero_mb takes it, 1 or 2; anything else is
+    refused by name (host only: no device is touched)."""
+    mod = rot.aeroServoMod
+    if mod not in (1, 2):
+        raise NotImplementedError(f"device aero-servo matrices: rotor {ir} has aeroServoMod = {mod} (1 or 2)")
+    return int(mod)
+
+
+def aero_param_row(rot, speed, mode):
+    """The rh_rotor_aero_mb parameter row of one (case, rotor) pair at the rotor's current pose and
+    yaw (after Rotor.inflow_angles of the case): everything Rotor.calcAero and
+    FOWT.calcTurbineConstants use that does not depend on the bin.  The gains are interpolated at
+    the case's wind speed and the torque gains gated as calcAero does; the gyroscopic vector takes
+    the rotor speed at `speed`, not at Uhub, as calcTurbineConstants has it."""
+    row = np.zeros(N.AP_COUNT)
+    row[N.AP["MODE"]] = mode
+    row[N.AP["RQ"]:N.AP["RQ"] + 9] = np.asarray(rot.R_q, dtype=float).reshape(9)
+    row[N.AP["RHUB"]:N.AP["RHUB"] + 3] = rot.r_hub_rel
+    kp_beta = -np.interp(speed, rot.Uhub, rot.kp_0)
+    ki_beta = -np.interp(speed, rot.Uhub, rot.ki_0)
+    row[N.AP["I_DRIVETRAIN"]], row[N.AP["NG"]], row[N.AP["K_FLOAT"]] = rot.I_drivetrain, rot.Ng, rot.k_float
+    row[N.AP["KP_BETA"]], row[N.AP["KI_BETA"]] = kp_beta, ki_beta
+    row[N.AP["KP_TAU"]], row[N.AP["KI_TAU"]] = rot.kp_tau * (kp_beta == 0), rot.ki_tau * (ki_beta == 0)
+    Omega_rpm = np.interp(speed, rot.Uhub, rot.Omega_rpm)
+    row[N.AP["GYRO"]:N.AP["GYRO"] + 3] = rot.I_drivetrain * (rot.q * Omega_rpm * 2 * np.pi / 60)
+    return row
+
+
 class DeviceRotor:
     """One or more rotors resident on the device; operating points pick a rotor through rot_idx."""
 
@@ -174,6 +203,38 @@ class DeviceRotor:
                                        N.ptr(idx), N.ptr(op), N.ptr(loads), N.ptr(dloads), N.ptr(sec), N.ptr(status),
                                        N.stream_handle(torch, self.device)), "rh_rotor_loads")
         return dict(loads=loads, dloads=dloads, sec=sec, status=status, _keep=(op, idx))
+
+    def aero_mb(self, res, ncase, pair_case, modes, param, w, M0, B0):
+        """rh_rotor_aero_mb on the stream of launch(): res its result for the pairs (with
+        derivatives), consumed on the device; pair_case [npair] the case row of each pair
+        (non-decreasing, the pairs of a case in rotor order), modes [npair] their aeroServoMod,
+        param [npair, AP_COUNT] their rows (aero_param_row); w [nw], M0, B0 ([6, 6] or [nw, 6, 6])
+        device tensors of the base design.  Returns device tensors M [ncase, nw, 6, 6],
+        B [ncase, nw, 6, 6] and f_aero0 [ncase, 6]."""
+        torch = self.torch
+        pc = np.ascontiguousarray(pair_case, dtype=np.int32)
+        md = np.ascontiguousarray(modes, dtype=np.int32)
+        par = np.ascontiguousarray(param, dtype=np.float64)
+        npair, nw = len(pc), int(w.shape[0])
+        if md.shape != (npair,) or par.shape != (npair, N.AP_COUNT) or res["loads"].shape[0] != npair \
+                or res["dloads"] is None:
+            raise ValueError("aero_mb: one mode, parameter row and rh_rotor_loads row (with derivatives) per pair expected")
+        if not np.array_equal(par[:, N.AP["MODE"]], md):     # the kernel reads the table's, the entry validates md
+            raise ValueError("aero_mb: the parameter rows' mode column differs from modes")
+        per_bin = M0.dim() == 3
+        if tuple(M0.shape) != ((nw, 6, 6) if per_bin else (6, 6)) or B0.shape != M0.shape:
+            raise ValueError(f"aero_mb: M0 and B0 of shape [6, 6] or [{nw}, 6, 6] expected")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        pc_dev = torch.tensor(pc, dtype=torch.int32, device=self.device)
+        par_dev = torch.tensor(par, **f64)
+        M = torch.empty([ncase, nw, 6, 6], **f64)
+        B = torch.empty([ncase, nw, 6, 6], **f64)
+        f0 = torch.empty([ncase, 6], **f64)
+        N.check(N.lib().rh_rotor_aero_mb(N.context(self.dev_index), ncase, npair, nw, N.ptr(w), N.ptr(pc_dev),
+                                         pc.ctypes.data, md.ctypes.data, N.ptr(res["loads"]), N.ptr(res["dloads"]),
+                                         N.ptr(par_dev), N.ptr(M0), N.ptr(B0), int(per_bin), N.ptr(M), N.ptr(B),
+                                         N.ptr(f0), N.stream_handle(torch, self.device)), "rh_rotor_aero_mb")
+        return dict(M=M, B=B, f_aero0=f0, _keep=(pc_dev, par_dev, res))
 
     def evaluate(self, rot_idx, Uinf, Omega_rpm, pitch_deg, tilt, yaw, derivatives=True, sections=False):
         """CCBlade.evaluate of every operating point (tilt and yaw [rad] as Rotor.runCCBlade sets
