@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from .hydro_math import get_from_dict
-from .model import Model
+from .model import CaseMB, Model
 from .second_order import solve_batch_2nd
 from .solver import CaseSet
 
@@ -187,9 +187,6 @@ class DesignBatch:
     def _aero_views(self, design_idx, cases):
         """(views, per-case view index, the FOWT of each view) when some case has an operating
         rotor, else None."""
-        import torch
-        from .model import CaseMB
-        from .prep import linear_matrices
         hot = [i for i, c in enumerate(cases) if not isinstance(self.fowts[int(design_idx[i])], HostDesign)
                and Model._operating_rotor(self.fowts[int(design_idx[i])], c)]
         if not hot:
@@ -210,12 +207,9 @@ class DesignBatch:
             key = (d, tuple(sorted((k, str(v)) for k, v in c.items() if k not in self._WAVE_KEYS)))
             if key not in made:
                 fowt = self.fowts[d]
-                fowt.calcTurbineConstants(dict(c), ptfm_pitch=0)
-                M, B, _, _ = linear_matrices(fowt)
+                views.append(CaseMB.of_case(fowt, self.dds[d], c))
                 fowt.calcTurbineConstants(dict(c, wind_speed=0.0), ptfm_pitch=0)     # back to the aero-free design
-                f64 = dict(dtype=torch.float64, device=self.dds[d].device)
                 self.dds[d].ensure_headings(heads)
-                views.append(CaseMB(self.dds[d], torch.tensor(M, **f64).contiguous(), torch.tensor(B, **f64).contiguous()))
                 owners.append(fowt)
                 made[key] = len(views) - 1
             idx[i] = made[key]

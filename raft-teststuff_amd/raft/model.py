@@ -22,7 +22,7 @@ import numpy as np
 from . import _native as N
 from .fowt import FOWT, mooring_outputs
 from .hydro_math import DEG2RAD, get_from_dict, wave_numbers
-from .second_order import file_qtf_forces, qtf_index_error, solve_batch_2nd
+from .second_order import file_qtf_forces, qtf_index_error, sea_spectra, solve_batch_2nd
 from .solver import BatchResult, CaseSet, solve_batch
 
 
@@ -32,6 +32,17 @@ class CaseMB:
 
     def __init__(self, base, M, B):
         self.base, self._M, self._B = base, M, B
+
+    @classmethod
+    def of_case(cls, fowt, base, case, bem=None):
+        """The view of `base` with the M and B that calcTurbineConstants(case, bem=bem) gives `fowt`,
+        which is left with that case's turbine constants."""
+        import torch
+        from .prep import linear_matrices
+        fowt.calcTurbineConstants(dict(case), ptfm_pitch=0, bem=bem)
+        M, B, _, _ = linear_matrices(fowt)
+        f64 = dict(dtype=torch.float64, device=base.device)
+        return cls(base, torch.tensor(M, **f64).contiguous(), torch.tensor(B, **f64).contiguous())
 
     def __getattr__(self, name):
         return getattr(self.__dict__["base"], name)
@@ -43,6 +54,36 @@ class CaseMB:
         d = N.RhDesign.from_buffer_copy(self.base.struct())
         d.M, d.B, d.mb_per_bin = N.ptr(self._M), N.ptr(self._B), 1
         return d
+
+
+class FurtherSeaStates:
+    """The sea states after the first of every case of a batch (raft/raft_model.py:1049-1065), case
+    after case.  seas: _case_sea_states of every case, nws their sea-state counts.  Host only:
+    pairs [(case, sea state)], case / sea their index arrays, the picked columns heading [deg],
+    spectrum, Hs, Tp, gamma, betas [rad] and nwm, the batch's largest sea-state count."""
+
+    def __init__(self, seas, nws):
+        self.pairs = [(i, h) for i in range(len(seas)) for h in range(1, int(nws[i]))]
+        self.case = np.array([i for i, _ in self.pairs], dtype=np.int64)
+        self.sea = np.array([h for _, h in self.pairs], dtype=np.int64)
+        self.heading, self.spectrum, self.Hs, self.Tp, self.gamma = ([seas[i][k][h] for i, h in self.pairs]
+                                                                     for k in range(5))
+        self.betas = np.array(self.heading, dtype=float) * DEG2RAD
+        self.nwm = int(max(nws)) if len(nws) else 0
+
+    def spectra(self, dd):
+        """S and zeta [m, nw] of the pairs on design dd's grid (rh_sea_state, one launch)."""
+        return sea_spectra(dd, [N.SPECTRUM_CODES[x] for x in self.spectrum], self.Hs, self.Tp, self.gamma)
+
+    def scatter(self, first, further, rows):
+        """[n, rows, ...] in the reference's layout: row 0 of case i is first[i], row h the entry of
+        further [m, ...] for the pair (i, h); rows of absent sea states are zero."""
+        import torch
+        out = torch.zeros([first.shape[0], rows, *first.shape[1:]], dtype=first.dtype, device=first.device)
+        out[:, 0] = first
+        out[torch.tensor(self.case, dtype=torch.long, device=first.device),
+            torch.tensor(self.sea, dtype=torch.long, device=first.device)] = further
+        return out
 
 
 class Model:
@@ -285,9 +326,7 @@ class Model:
             K_hs.append(fowt.C_struc + fowt.C_hydro)
             F_und[6 * i:6 * i + 6] += fowt.W_struc + fowt.W_hydro
             if case:
-                ci = dict(case)
-                if isinstance(case.get("wind_speed"), list):
-                    ci["wind_speed"] = case["wind_speed"][i]
+                ci = self._fowt_case(case, i)
                 fowt.calcTurbineConstants(ci, ptfm_pitch=0)
                 fowt.calcHydroConstants()
                 F_env[6 * i:6 * i + 6] = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
@@ -357,9 +396,43 @@ class Model:
                       f"{fowt.Xi0[1]: .2f},  and heave = {fowt.Xi0[2]: .2f} m")
         return X
 
-    def _statics_batch_inputs(self, cases, F_extra=None, rotor_device=False):
+    @staticmethod
+    def _fowt_case(case, i):
+        """A copy of a case as FOWT i sees it: a per-FOWT wind_speed list reduced to its entry i."""
+        ci = dict(case)
+        if isinstance(case.get("wind_speed"), list):
+            ci["wind_speed"] = case["wind_speed"][i]
+        return ci
+
+    def _reference_poses(self):
+        """X_ref [nFOWT, 6] of the FOWTs."""
+        return np.array([[f.x_ref, f.y_ref, 0, 0, 0, 0] for f in self.fowtList], dtype=float)
+
+    def _array_rotor_loads(self, cases):
+        """[FOWT][case] bem arguments: FOWT.rotorLoadsBatch of every FOWT at its current pose, one launch each."""
+        return [fowt.rotorLoadsBatch([self._fowt_case(c, i) for c in cases], self.device)
+                for i, fowt in enumerate(self.fowtList)]
+
+    def _mean_loads(self, cases, F_und, bems=None):
+        """F_const [n, nFOWT, 6] = F_und [nFOWT, 6] + F_env of every (case, FOWT) at the FOWTs' current
+        poses, F_env built as solveStatics builds it: the mean aero loads (bems[FOWT][case]: the rotors'
+        loads from the device, else the host evaluates), current drag and the mean wave drift."""
+        F_const = np.zeros([len(cases), self.nFOWT, 6])
+        for ic, case in enumerate(cases):
+            for i, fowt in enumerate(self.fowtList):
+                ci = self._fowt_case(case, i)
+                fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i][ic] if bems else None)
+                F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
+                if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
+                    F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
+                F_const[ic, i] = F_und[i] + F_env
+        return F_const
+
+    def _statics_batch_inputs(self, cases, F_extra=None, bems=None):
         """The host side of solveStaticsBatch: the device mooring system, X_ref [6], K_hs [6,6],
-        F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref."""
+        F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref.
+        bems: None (the host evaluates the rotors), or a list, filled here after every refusal with the
+        rotors' device loads at X_ref (_array_rotor_loads) for the caller that needs them again."""
         from .mooring_device import DeviceMooring, warm_state
         if self.nFOWT != 1 or self.ms is not None:
             raise NotImplementedError("solveStaticsBatch: a single FOWT with its own mooring system (arrays and "
@@ -367,7 +440,6 @@ class Model:
         fowt = self.fowtList[0]
         if fowt.ms is None:
             raise NotImplementedError("solveStaticsBatch: the FOWT has no mooring system")
-        n = len(cases)
         if self.mooring_currentMod > 0 and any(get_from_dict(c, "current_speed", shape=0, default=0.0) > 0
                                                for c in cases):
             raise NotImplementedError("solveStaticsBatch: current on the mooring lines (mooring currentMod 1)")
@@ -375,23 +447,16 @@ class Model:
         if getattr(self, "_moor_dev", None) is None or self._moor_dev[0] is not fowt.ms:
             self._moor_dev = (fowt.ms, DeviceMooring([fowt.ms], self.device))
         dm = self._moor_dev[1]
-        X_ref = np.array([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0], dtype=float)
+        X_ref = self._reference_poses()[0]
         fowt.setPosition(X_ref)
         fowt.calcStatics()
         K_hs = fowt.C_struc + fowt.C_hydro
-        F_und = fowt.W_struc + fowt.W_hydro
         warm0 = warm_state(fowt.ms)                      # the line solutions at the reference pose
-        F_const = np.zeros([n, 6])
-        bems = fowt.rotorLoadsBatch([dict(c) for c in cases], self.device) if rotor_device else None
-        for i, case in enumerate(cases):
-            ci = dict(case)
-            fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i] if bems else None)
-            F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
-            if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
-                F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
-            F_const[i] = F_und + F_env
-            if F_extra is not None:
-                F_const[i] += np.asarray(F_extra[i], dtype=float)
+        if bems is not None:
+            bems[:] = self._array_rotor_loads(cases)
+        F_const = self._mean_loads(cases, [fowt.W_struc + fowt.W_hydro], bems)[:, 0]
+        if F_extra is not None:
+            F_const += np.asarray(F_extra, dtype=float).reshape(len(cases), 6)
         return dm, X_ref, K_hs, F_const, warm0
 
     def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False):
@@ -405,7 +470,11 @@ class Model:
         tensors with host=False.  The model is left at its reference pose.  rotor_device=True takes the
         rotors' blade-element loads of all cases from one device launch (FOWT.rotorLoadsBatch) instead of
         one host CCBlade evaluation per case; a case whose rotor solve fails raises RuntimeError."""
-        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, rotor_device)
+        return self._solve_statics_batch(cases, F_extra, host, [] if rotor_device else None)
+
+    def _solve_statics_batch(self, cases, F_extra, host, bems):
+        """solveStaticsBatch with the rotor loads as _statics_batch_inputs takes them."""
+        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, bems)
         n = len(cases)
         sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)))
         ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True)
@@ -415,11 +484,11 @@ class Model:
                    F_moor=ev["F"], C_moor=ev["K"], Tmoor_avg=ev["T"], J_moor=ev["J"], iters=sol["iters"], status=status)
         return {k: v.cpu().numpy() for k, v in out.items()} if host else out
 
-    def _statics_array_inputs(self, cases, F_extra=None, rotor_device=False):
+    def _statics_array_inputs(self, cases, F_extra=None, bems=None):
         """The host side of solveStaticsArrayBatch: the merged record and one record per system,
         X_ref [N,6], K_hs [N,6,6], F_const [n,N,6] and the state (line warm starts, free
         points) of every system with the FOWTs at their reference poses.  Every refusal is raised
-        before the device is touched."""
+        before the device is touched.  bems: as _statics_batch_inputs takes it."""
         from .mooring_array_device import array_state, flatten_array
         own = [f.ms for f in self.fowtList]
         if self.ms is None and all(s is None for s in own):
@@ -439,10 +508,9 @@ class Model:
         subs = [rec] if len(rec.systems) == 1 else [rec] + [flatten_array([(ms, range(len(ms.bodies)))])
                                                             for ms, _ in rec.systems]
         nf, n = self.nFOWT, len(cases)
-        X_ref = np.zeros([nf, 6])
+        X_ref = self._reference_poses()
         K_hs, F_und = np.zeros([nf, 6, 6]), np.zeros([nf, 6])
         for i, fowt in enumerate(self.fowtList):
-            X_ref[i, :2] = fowt.x_ref, fowt.y_ref
             fowt.setPosition(X_ref[i])
             fowt.calcStatics()
             K_hs[i] = fowt.C_struc + fowt.C_hydro
@@ -450,36 +518,17 @@ class Model:
         if self.ms is not None:
             self.ms.set_body_positions(list(X_ref))
         warm0, free0 = array_state(rec)                  # the state at the reference poses, read once
-        F_const = np.zeros([n, nf, 6])
-        bems = self._array_rotor_loads(cases) if rotor_device else None
-        for ic, case in enumerate(cases):
-            for i, fowt in enumerate(self.fowtList):
-                ci = dict(case)
-                if isinstance(case.get("wind_speed"), list):
-                    ci["wind_speed"] = case["wind_speed"][i]
-                fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i][ic] if bems else None)
+        if bems is not None:
+            bems[:] = self._array_rotor_loads(cases)
+        F_const = self._mean_loads(cases, F_und, bems)
+        if n:
+            # the members' added mass at the reference pose, as solveStatics leaves it (once per FOWT: it
+            # reads the pose alone, and neither the turbine constants nor the current loads read its results)
+            for fowt in self.fowtList:
                 fowt.calcHydroConstants()
-                F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
-                if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
-                    F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
-                F_const[ic, i] = F_und[i] + F_env
         if F_extra is not None:
             F_const += np.asarray(F_extra, dtype=float).reshape(n, nf, 6)
         return rec, subs, X_ref, K_hs, F_const, warm0, free0
-
-    def _array_rotor_loads(self, cases):
-        """FOWT.rotorLoadsBatch of every FOWT at its current pose, a per-FOWT wind-speed list of a
-        case read as the statics loops read it.  Returns [FOWT][case] bem arguments."""
-        out = []
-        for i, fowt in enumerate(self.fowtList):
-            cs = []
-            for case in cases:
-                ci = dict(case)
-                if isinstance(case.get("wind_speed"), list):
-                    ci["wind_speed"] = case["wind_speed"][i]
-                cs.append(ci)
-            out.append(fowt.rotorLoadsBatch(cs, self.device))
-        return out
 
     def solveStaticsArrayBatch(self, cases, F_extra=None, host=True, rotor_device=False):
         """The mean offsets of many load cases of N >= 1 FOWTs moored by the array-level system and / or
@@ -495,8 +544,12 @@ class Model:
         iters [n] (evaluations: len(Model.Xs2) of the host path), status [n] (0 = converged, else
         _native.MOOR_STATUS); numpy arrays, or device tensors with host=False.  The model is left at
         its reference pose.  rotor_device: as solveStaticsBatch, one launch per FOWT."""
+        return self._solve_statics_array_batch(cases, F_extra, host, [] if rotor_device else None)
+
+    def _solve_statics_array_batch(self, cases, F_extra, host, bems):
+        """solveStaticsArrayBatch with the rotor loads as _statics_batch_inputs takes them."""
         from .mooring_array_device import DeviceArrayMooring
-        rec, subs, X_ref, K_hs, F_const, warm0, free0 = self._statics_array_inputs(cases, F_extra, rotor_device)
+        rec, subs, X_ref, K_hs, F_const, warm0, free0 = self._statics_array_inputs(cases, F_extra, bems)
         # the device records are kept between calls while the freshly flattened tables equal theirs
         dm = getattr(self, "_moor_arr_dev", None)
         if dm is None or dm.dev_index != self.device or not dm.same_tables(subs):
@@ -557,6 +610,54 @@ class Model:
         cpu = lambda v: None if v is None else v.cpu().numpy()   # noqa: E731
         return {k: [cpu(x) for x in v] if isinstance(v, list) else cpu(v) for k, v in out.items()}
 
+    # the steps analyzeCasesBatch(statics=True) and analyzeArrayBatch(statics=True) share
+    def _refuse_pose_analysis(self, who, cases, pose_chunk):
+        """What `who`(statics=True) refuses, before the device is touched.  Returns the cases' sea states."""
+        array = who == "analyzeArrayBatch"
+        if any(f.potSecOrder > 0 for f in self.fowtList):
+            raise NotImplementedError(f"{who}(statics=True): potSecOrder > 0 (the reference solves the "
+                                      "statics twice around the dynamics, raft/raft_model.py:301-318)")
+        if (array and self.K_array is not None) or any("C_moor" in (f._statics or {}) for f in self.fowtList):
+            raise NotImplementedError(f"{who}(statics=True): the mooring stiffness was given as a fixture "
+                                      f"({'K_array, or ' if array else ''}setStatics with a C_moor): there is no system "
+                                      "to solve")
+        if int(pose_chunk) < 1:
+            raise ValueError("pose_chunk must be >= 1")
+        seas = [self._case_sea_states(c) for c in cases]
+        if any(len(s[0]) > 1 for s in seas):
+            raise NotImplementedError(f"{who}(statics=True): several sea states per case")
+        return seas
+
+    @staticmethod
+    def _design_at_pose(fowt, case, X_ref, X, bem, moor, headings):
+        """The DeviceDesign of one (case, FOWT) at its solved pose X, with `headings` [deg] tabulated:
+        the FOWT is moved there exactly as solveStatics leaves it, turbine and hydro constants at the
+        reference pose, members and rotors at the offset pose, and C_moor and F_moor0 of its own
+        mooring system from the device (moor; None without one)."""
+        fowt.setPosition(X_ref)
+        fowt.calcTurbineConstants(case, ptfm_pitch=0, bem=bem)
+        fowt.calcHydroConstants()
+        fowt.setPosition(X)
+        if moor is not None:
+            fowt.C_moor, fowt.F_moor0 = moor[0].copy(), moor[1].copy()
+        fowt._dd = fowt._host = None
+        dd = fowt.device_design()
+        dd.ensure_headings(np.asarray(headings, dtype=float) * DEG2RAD)
+        return dd
+
+    def _restore_reference_poses(self, X_ref):
+        """Every FOWT back at its reference pose, the design of its last solved pose dropped."""
+        for fowt, x in zip(self.fowtList, X_ref):
+            fowt.setPosition(x)
+            fowt._dd = fowt._host = None
+
+    def _tension_channels(self, J, Xi):
+        """Tmoor_PSD [n, 2L, nw] and Tmoor_std [n, 2L] of mooring_outputs: the tension amplitudes J Xi,
+        the PSD over w[0] as the reference has it."""
+        import torch
+        a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2   # [n, 2L, nw]
+        return 0.5 * a2 / float(self.w[0]), torch.sqrt(0.5 * a2.sum(dim=2))
+
     def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False):
         """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
         analyzeCases solves it when the mooring is a system.  Offsets, C_moor and the tension
@@ -569,56 +670,31 @@ class Model:
             raise NotImplementedError("analyzeCasesBatch(statics=True): arrays (their statics couple the FOWTs; "
                                       "use analyzeCases)")
         fowt = self.fowtList[0]
-        if fowt.potSecOrder > 0:
-            raise NotImplementedError("analyzeCasesBatch(statics=True): potSecOrder > 0 (the reference solves the "
-                                      "statics twice around the dynamics, raft/raft_model.py:301-318)")
-        if "C_moor" in (fowt._statics or {}):
-            raise NotImplementedError("analyzeCasesBatch(statics=True): the mooring stiffness was given as a fixture "
-                                      "(setStatics with a C_moor): there is no system to solve")
-        if int(pose_chunk) < 1:
-            raise ValueError("pose_chunk must be >= 1")
-        seas = [self._case_sea_states(c) for c in cases]
-        if any(len(s[0]) > 1 for s in seas):
-            raise NotImplementedError("analyzeCasesBatch(statics=True): several sea states per case")
+        seas = self._refuse_pose_analysis("analyzeCasesBatch", cases, pose_chunk)
         self._calc_bem_once()
-        sb = self.solveStaticsBatch(cases, host=False, rotor_device=rotor_device)
-        # (the model is at its reference pose here, where the loop below takes the turbine constants)
-        bems = fowt.rotorLoadsBatch([dict(c) for c in cases], self.device) if rotor_device else None
+        # (the rotor loads are those of the reference pose, where _design_at_pose takes the turbine constants)
+        bems = [] if rotor_device else None
+        sb = self._solve_statics_batch(cases, None, False, bems)
         X = sb["X"].cpu().numpy()
         C = sb["C_moor"].cpu().numpy()
         Fm = sb["F_moor"].cpu().numpy()
-        X_ref = np.array([fowt.x_ref, fowt.y_ref, 0, 0, 0, 0], dtype=float)
+        X_ref = self._reference_poses()
         n = len(cases)
         parts = []
         for c0 in range(0, n, int(pose_chunk)):
             ids = range(c0, min(n, c0 + int(pose_chunk)))
-            views = []
-            for i in ids:
-                fowt.setPosition(X_ref)
-                fowt.calcTurbineConstants(dict(cases[i]), ptfm_pitch=0, bem=bems[i] if bems else None)
-                fowt.calcHydroConstants()
-                fowt.setPosition(X[i])
-                fowt.C_moor, fowt.F_moor0 = C[i].copy(), Fm[i].copy()
-                fowt._dd = fowt._host = None
-                dd = fowt.device_design()
-                dd.ensure_headings(np.asarray(seas[i][0], dtype=float) * DEG2RAD)
-                views.append(dd)
+            views = [self._design_at_pose(fowt, self._fowt_case(cases[i], 0), X_ref[0], X[i], bems[0][i] if bems else None,
+                                          (C[i], Fm[i]), seas[i][0]) for i in ids]
             hd, sp, Hs, Tp, gm = ([seas[i][k][0] for i in ids] for k in range(5))
             cs = CaseSet(np.arange(len(views), dtype=np.int32), hd, sp, Hs, Tp, gm)
             res = solve_batch(views, cs, self.nIter, self.XiStart, tol, want=tuple(want))
             parts.append({k: v.clone() for k, v in res.items()})
             torch.cuda.synchronize(views[0].device)      # the chunk's tables are released below
             del res, views
-        fowt.setPosition(X_ref)
-        fowt._dd = fowt._host = None
+        self._restore_reference_poses(X_ref)
         res = BatchResult({k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]} if parts else {})
         if n:
-            # tension channels (mooring_outputs): amplitudes J_moor Xi, PSD over w[0] as the reference has it
-            Xi = res["Xi"]
-            J = sb["J_moor"]
-            a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2   # [n, 2L, nw]
-            res["Tmoor_PSD"] = 0.5 * a2 / float(self.w[0])
-            res["Tmoor_std"] = torch.sqrt(0.5 * a2.sum(dim=2))
+            res["Tmoor_PSD"], res["Tmoor_std"] = self._tension_channels(sb["J_moor"], res["Xi"])
             res["Tmoor_avg"] = sb["Tmoor_avg"]
             res["mean_offsets"] = sb["X"]
             res["statics_iters"] = sb["iters"]
@@ -822,50 +898,36 @@ class Model:
         hd, sp, Hs, Tp, gm = ([s[k][0] for s in seas] for k in range(5))
         multi = len(cases) > 0 and nws.max() > 1
         want_fp = tuple(want) + (("Bmat", "B_drag") if multi else ())
-        aero = [self._operating_rotor(fowt, c) for c in cases]
-        if multi:   # every heading tabulated before the fixed point (its tables stay put)
+        sel = [i for i, c in enumerate(cases) if self._operating_rotor(fowt, c)]
+        if multi:  # every heading tabulated before the fixed point (its tables stay put)
             fowt.device_design().ensure_headings(np.concatenate([np.asarray(s[0], dtype=float) for s in seas]) * DEG2RAD)
-        if not any(aero):
-            views = [fowt.device_design()]
-            cs = CaseSet(np.zeros(len(cases), dtype=np.int32), hd, sp, Hs, Tp, gm)
-            res = solve_batch_2nd(views, [fowt], cs, self.nIter, self.XiStart, tol, want=want_fp)
-            if multi:
-                self._extra_sea_states(res, views, cs.design_idx, seas, nws, want)
-            if aero_device:
-                import torch
-                res["f_aero0"] = torch.zeros([len(cases), 6], dtype=torch.float64, device=views[0].device)
-            return res.host() if host else res
-        # operating rotors: each such case gets its own per-bin M and B (its rotors' aero-servo
-        # added mass and damping, FOWT.calcTurbineConstants) on the shared node and wave tables
-        import torch
-        from .prep import linear_matrices
-        fowt.calcTurbineConstants(dict(cases[0], wind_speed=0.0), ptfm_pitch=0)     # the aero-free design
+        if sel:     # (a batch without an operating rotor leaves the turbine constants as they are)
+            fowt.calcTurbineConstants(dict(cases[0], wind_speed=0.0), ptfm_pitch=0)     # the aero-free design
         base = fowt.device_design()
-        base.ensure_headings(np.unique(np.asarray(hd, dtype=float)) * DEG2RAD)
         views, idx = [base], np.zeros(len(cases), dtype=np.int32)
-        bems = {}
-        sel = [i for i in range(len(cases)) if aero[i]]
         mb = None
-        if aero_device:      # every wind case's M and B from two launches; its CaseMB views a row of them
-            mb = fowt.aeroMBBatch([dict(cases[i]) for i in sel], base, self.device)
-            if mb is not None:
-                for row, i in enumerate(sel):
-                    views.append(CaseMB(base, mb["M"][row], mb["B"][row]))
+        if sel:
+            # operating rotors: each such case gets its own per-bin M and B (its rotors' aero-servo
+            # added mass and damping, FOWT.calcTurbineConstants) on the shared node and wave tables
+            base.ensure_headings(np.unique(np.asarray(hd, dtype=float)) * DEG2RAD)
+            if aero_device:      # every wind case's M and B from two launches; its CaseMB views a row of them
+                mb = fowt.aeroMBBatch([dict(cases[i]) for i in sel], base, self.device)
+                if mb is not None:
+                    for row, i in enumerate(sel):
+                        views.append(CaseMB(base, mb["M"][row], mb["B"][row]))
+                        idx[i] = len(views) - 1
+            else:
+                bems = dict(zip(sel, fowt.rotorLoadsBatch([dict(cases[i]) for i in sel], self.device))) \
+                    if rotor_device else {}
+                for i in sel:
+                    views.append(CaseMB.of_case(fowt, base, cases[i], bems.get(i)))
                     idx[i] = len(views) - 1
-        elif rotor_device:
-            bems = dict(zip(sel, fowt.rotorLoadsBatch([dict(cases[i]) for i in sel], self.device)))
-        for i, c in enumerate(cases):
-            if aero[i] and not aero_device:
-                fowt.calcTurbineConstants(dict(c), ptfm_pitch=0, bem=bems.get(i))
-                M, B, _, _ = linear_matrices(fowt)
-                f64 = dict(dtype=torch.float64, device=base.device)
-                views.append(CaseMB(base, torch.tensor(M, **f64).contiguous(), torch.tensor(B, **f64).contiguous()))
-                idx[i] = len(views) - 1
         cs = CaseSet(idx, hd, sp, Hs, Tp, gm)
         res = solve_batch_2nd(views, [fowt] * len(views), cs, self.nIter, self.XiStart, tol, want=want_fp)
         if multi:
             self._extra_sea_states(res, views, idx, seas, nws, want)
         if aero_device:
+            import torch
             f0 = torch.zeros([len(cases), 6], dtype=torch.float64, device=base.device)
             if mb is not None:
                 f0[torch.tensor(sel, dtype=torch.long, device=base.device)] = mb["f_aero0"]
@@ -905,52 +967,37 @@ class Model:
         (rh_motion_stats, getPSD / getRMS of raft/raft_fowt.py:1831-1875)."""
         import torch
         n, nw = len(seas), self.nw
-        nwm = int(nws.max())
+        ext = FurtherSeaStates(seas, nws)
         dd = views[0]
         dev = dd.device
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        ext = [(i, h) for i in range(n) for h in range(1, int(nws[i]))]
-        ci = np.array([i for i, _ in ext], dtype=np.int64)
-        pick = lambda k: [seas[i][k][h] for i, h in ext]   # noqa: E731
-        betas = np.array(pick(0), dtype=float) * DEG2RAD
-        heads = dd.ensure_headings(betas)
+        heads = dd.ensure_headings(ext.betas)
         ctx, s = N.context(self.device), N.stream_handle(torch, dev)
-        m = len(ext)
-        S = torch.empty([m, nw], **f64)
-        zeta = torch.empty([m, nw], **f64)
-        spec = torch.tensor([N.SPECTRUM_CODES[x] for x in pick(1)], **i32)
-        Hs, Tp, gm = (torch.tensor(pick(k), **f64) for k in (2, 3, 4))
-        N.check(N.lib().rh_sea_state(ctx, m, nw, N.ptr(dd.w), float(dd.dw), N.ptr(spec), N.ptr(Hs), N.ptr(Tp),
-                                     N.ptr(gm), N.ptr(S), N.ptr(zeta), s), "rh_sea_state")
-        sel = torch.tensor(ci, dtype=torch.long, device=dev)
+        m = len(ext.pairs)
+        S, zeta = ext.spectra(dd)
+        sel = torch.tensor(ext.case, dtype=torch.long, device=dev)
         bdrag = res["B_drag"].index_select(0, sel).contiguous()
         bmat = res["Bmat"].index_select(0, sel).contiguous()
         XiE = torch.empty([m, 6, nw], dtype=torch.complex128, device=dev)
         fext = None
         fowt = self.fowtList[0]
         if fowt.potSecOrder == 2:      # the .12d QTF's force of each further sea state (:1059-1061)
-            fext, fm = file_qtf_forces(dd, fowt, betas, S)
-            fw = torch.zeros([n, nwm, 6], **f64)
-            fw[:, 0] = res["f2nd_mean"]
-            fw[sel, torch.tensor([h for _, h in ext], dtype=torch.long, device=dev)] = fm
-            res["f2nd_mean_waves"] = fw
+            fext, fm = file_qtf_forces(dd, fowt, ext.betas, S)
+            res["f2nd_mean_waves"] = ext.scatter(res["f2nd_mean"], fm, ext.nwm)
         arr = (N.RhDesign * len(views))(*[v.struct() for v in views])
         # (the index tensors are held in names: a temporary freed before the call returns would
         # hand its block to the next allocation, and the kernel would read the other array)
-        didx = torch.tensor(np.asarray(idx)[ci], **i32)
+        didx = torch.tensor(np.asarray(idx)[ext.case], **i32)
         hidx = torch.tensor(heads, **i32)
         N.check(N.lib().rh_heading_response_ext(ctx, arr, len(views), m, N.ptr(didx), N.ptr(hidx), N.ptr(zeta),
                                                 N.ptr(bdrag), N.ptr(bmat), int(bmat.shape[1]), N.ptr(fext), N.ptr(XiE),
                                                 s), "rh_heading_response_ext")
-        Xw = torch.zeros([n, nwm + 1, 6, nw], dtype=torch.complex128, device=dev)
-        Xw[:, 0] = res["Xi"]
-        Xw[sel, torch.tensor([h for _, h in ext], dtype=torch.long, device=dev)] = XiE
-        res["Xi_waves"] = Xw
+        res["Xi_waves"] = Xw = ext.scatter(res["Xi"], XiE, ext.nwm + 1)
         if "psd" in want or "std" in want:
             psd = torch.empty([n, 6, nw], **f64)
             std = torch.empty([n, 6], **f64)
-            N.check(N.lib().rh_motion_stats(ctx, n, nwm + 1, nw, float(dd.dw), N.ptr(Xw), N.ptr(psd), N.ptr(std), s),
+            N.check(N.lib().rh_motion_stats(ctx, n, ext.nwm + 1, nw, float(dd.dw), N.ptr(Xw), N.ptr(psd), N.ptr(std), s),
                     "rh_motion_stats")
             res["psd"], res["std"] = psd, std
         res["nWaves"] = torch.tensor(nws, dtype=torch.int64, device=dev)
@@ -989,7 +1036,7 @@ class Model:
         dev = dds[0].device
         from .solver import prepare_batch
         Ka = self.array_stiffness()
-        return dict(n=n, dds=dds, cs=cs, prep=prepare_batch(dds, cs), dev=dev, seas=seas, nws=nws,
+        return dict(n=n, dds=dds, cs=cs, prep=prepare_batch(dds, cs), dev=dev, nws=nws, ext=FurtherSeaStates(seas, nws),
                     arr=(N.RhDesign * nf)(*[d.struct() for d in dds]),
                     K=None if Ka is None else torch.tensor(Ka, dtype=torch.float64, device=dev).contiguous())
 
@@ -1074,46 +1121,25 @@ class Model:
         offset pose, its own system's C_moor from the device)."""
         import torch
         from .solver import prepare_batch
-        if any(f.potSecOrder > 0 for f in self.fowtList):
-            raise NotImplementedError("analyzeArrayBatch(statics=True): potSecOrder > 0 (the reference solves the "
-                                      "statics twice around the dynamics, raft/raft_model.py:301-318)")
-        if self.K_array is not None or any("C_moor" in (f._statics or {}) for f in self.fowtList):
-            raise NotImplementedError("analyzeArrayBatch(statics=True): the mooring stiffness was given as a fixture "
-                                      "(K_array, or setStatics with a C_moor): there is no system to solve")
-        if int(pose_chunk) < 1:
-            raise ValueError("pose_chunk must be >= 1")
-        seas = [self._case_sea_states(c) for c in cases]
-        if any(len(s[0]) > 1 for s in seas):
-            raise NotImplementedError("analyzeArrayBatch(statics=True): several sea states per case")
+        seas = self._refuse_pose_analysis("analyzeArrayBatch", cases, pose_chunk)
         self._calc_bem_once()
-        sb = self.solveStaticsArrayBatch(cases, host=False, rotor_device=rotor_device)
-        bems = self._array_rotor_loads(cases) if rotor_device else None   # (every FOWT at its reference pose)
+        # (the rotor loads are those of the reference poses, where _design_at_pose takes the turbine constants)
+        bems = [] if rotor_device else None
+        sb = self._solve_statics_array_batch(cases, None, False, bems)
         nf, n, nw = self.nFOWT, len(cases), self.nw
         Xs = sb["X"].cpu().numpy()
         Cm = [None if c is None else c.cpu().numpy() for c in sb["C_moor"]]
         Fm = [None if c is None else c.cpu().numpy() for c in sb["F_moor0"]]
-        X_ref = np.array([[f.x_ref, f.y_ref, 0, 0, 0, 0] for f in self.fowtList], dtype=float)
+        X_ref = self._reference_poses()
         dev = sb["X"].device
         ctx, s = N.context(self.device), N.stream_handle(torch, dev)
         parts = []
         for c0 in range(0, n, int(pose_chunk)):
             ids = list(range(c0, min(n, c0 + int(pose_chunk))))
-            dds = []
-            for i in ids:
-                for f, fowt in enumerate(self.fowtList):
-                    ci = dict(cases[i])
-                    if isinstance(ci.get("wind_speed"), list):
-                        ci["wind_speed"] = ci["wind_speed"][f]
-                    fowt.setPosition(X_ref[f])
-                    fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[f][i] if bems else None)
-                    fowt.calcHydroConstants()
-                    fowt.setPosition(Xs[i, 6 * f:6 * f + 6])
-                    if Cm[f] is not None:
-                        fowt.C_moor, fowt.F_moor0 = Cm[f][i].copy(), Fm[f][i].copy()
-                    fowt._dd = fowt._host = None
-                    dd = fowt.device_design()
-                    dd.ensure_headings(np.asarray(seas[i][0], dtype=float) * DEG2RAD)
-                    dds.append(dd)
+            dds = [self._design_at_pose(fowt, self._fowt_case(cases[i], f), X_ref[f], Xs[i, 6 * f:6 * f + 6],
+                                        bems[f][i] if bems else None, None if Cm[f] is None else (Cm[f][i], Fm[f][i]),
+                                        seas[i][0])
+                   for i in ids for f, fowt in enumerate(self.fowtList)]
             m = len(ids)
             rep = lambda k: [seas[i][k][0] for i in ids for _ in range(nf)]   # noqa: E731
             cs = CaseSet(np.arange(m * nf, dtype=np.int32), rep(0), rep(1), rep(2), rep(3), rep(4))
@@ -1133,17 +1159,12 @@ class Model:
                           "std": std.view(m, nf, 6)})
             torch.cuda.synchronize(dev)                   # the chunk's tables are released below
             del res, dds, prep, arr, K
-        for f, fowt in enumerate(self.fowtList):
-            fowt.setPosition(X_ref[f])
-            fowt._dd = fowt._host = None
+        self._restore_reference_poses(X_ref)
         out = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]} if parts else {}
         if n:
             out["mean_offsets"], out["statics_iters"], out["statics_status"] = sb["X"], sb["iters"], sb["status"]
-            if sb["J_moor"] is not None:      # array_mooring: amplitudes J_moor Xi, PSD over w[0] as the reference has it
-                Xi, J = out["Xi"], sb["J_moor"]
-                a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2
-                out["Tmoor_PSD"] = 0.5 * a2 / float(self.w[0])
-                out["Tmoor_std"] = torch.sqrt(0.5 * a2.sum(dim=2))
+            if sb["J_moor"] is not None:      # the reference's array_mooring channels
+                out["Tmoor_PSD"], out["Tmoor_std"] = self._tension_channels(sb["J_moor"], out["Xi"])
                 out["Tmoor_avg"] = sb["Tmoor_avg"]
                 out["Tmoor_max"] = out["Tmoor_avg"] + 3 * out["Tmoor_std"]
                 out["Tmoor_min"] = out["Tmoor_avg"] - 3 * out["Tmoor_std"]
@@ -1155,20 +1176,16 @@ class Model:
         step 2, a singular (sea state, bin) returns NaN rows, which its case's psd / std inherit."""
         import torch
         nf, n, nw = self.nFOWT, P["n"], self.nw
-        dds, dev, seas, nws = P["dds"], P["dev"], P["seas"], P["nws"]
-        nwm = int(nws.max())
+        dds, dev, nws, ext = P["dds"], P["dev"], P["nws"], P["ext"]
+        nwm = ext.nwm
         ctx, s = N.context(self.device), N.stream_handle(torch, dev)
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        ext = [(i, h) for i in range(n) for h in range(1, int(nws[i]))]
-        m = len(ext)
-        pick = lambda k: [seas[i][k][h] for i, h in ext]   # noqa: E731
-        betas = np.array(pick(0), dtype=float) * DEG2RAD
-        from .second_order import sea_spectra
-        S, zeta = sea_spectra(dds[0], [N.SPECTRUM_CODES[x] for x in pick(1)], pick(2), pick(3), pick(4))
+        m = len(ext.pairs)
+        S, zeta = ext.spectra(dds[0])
         # entries (extra sea state, FOWT), sea-state-major: the [m, 6 nf, nw] layout of the solve
-        src = np.array([i * nf + f for i, _ in ext for f in range(nf)], dtype=np.int64)
-        heads = np.array([dds[f].ensure_headings([b])[0] for b in betas for f in range(nf)], dtype=np.int32)
+        src = np.array([i * nf + f for i, _ in ext.pairs for f in range(nf)], dtype=np.int64)
+        heads = np.array([dds[f].ensure_headings([b])[0] for b in ext.betas for f in range(nf)], dtype=np.int32)
         didx = torch.tensor(np.tile(np.arange(nf, dtype=np.int32), m), **i32)
         hidx = torch.tensor(heads, **i32)
         srct = torch.tensor(src, dtype=torch.long, device=dev)
@@ -1180,25 +1197,17 @@ class Model:
                                            N.ptr(XE), s), "rh_wave_excitation")
         FE = XE.view(m, nf, 6, nw)
         if any(f.potSecOrder == 2 for f in self.fowtList):
-            fw = torch.zeros([n, nwm, nf, 6], **f64)
-            fw[:, 0] = out["f2nd_mean"]
-            hsel = torch.tensor([h for _, h in ext], dtype=torch.long, device=dev)
-            csel = torch.tensor([i for i, _ in ext], dtype=torch.long, device=dev)
+            fme = torch.zeros([m, nf, 6], **f64)
             for f, fowt in enumerate(self.fowtList):
                 if fowt.potSecOrder != 2:
                     continue
-                fx, fm = file_qtf_forces(dds[f], fowt, betas, S)          # (:1059-1061)
+                fx, fme[:, f] = file_qtf_forces(dds[f], fowt, ext.betas, S)          # (:1059-1061)
                 FE[:, f] += fx
-                fw[csel, hsel, f] = fm
-            out["f2nd_mean_waves"] = fw
+            out["f2nd_mean_waves"] = ext.scatter(out["f2nd_mean"], fme, nwm)
         N.check(N.lib().rh_array_solve_stats(ctx, P["arr"], nf, nf, m, N.ptr(didx), N.ptr(bdrag), N.ptr(P["K"]),
                                              N.ptr(XE), float(self.fowtList[0].dw), None, None, s),
                 "rh_array_solve_stats")
-        Xw = torch.zeros([n, nwm + 1, 6 * nf, nw], dtype=torch.complex128, device=dev)
-        Xw[:, 0] = X
-        Xw[torch.tensor([i for i, _ in ext], dtype=torch.long, device=dev),
-           torch.tensor([h for _, h in ext], dtype=torch.long, device=dev)] = XE
-        out["Xi_waves"] = Xw
+        out["Xi_waves"] = Xw = ext.scatter(X, XE, nwm + 1)
         out["nWaves"] = torch.tensor(nws, dtype=torch.int64, device=dev)
         rows = Xw.view(n, nwm + 1, nf, 6, nw).permute(0, 2, 1, 3, 4).contiguous()      # [n, nf, nW+1, 6, nw]
         psd = torch.empty([n * nf, 6, nw], **f64)

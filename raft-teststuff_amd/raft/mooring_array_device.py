@@ -13,6 +13,7 @@ than one system, more than ARR_MAX_BODIES bodies, ARR_MAX_FREE free points or MO
 import numpy as np
 
 from . import _native as N
+from .device_records import DeviceRecords
 from .mooring import MooringSystem, Point
 
 FIXED, ON_BODY, FREE = 0, 1, 2          # point kinds of the point table
@@ -104,7 +105,7 @@ def array_state(rec):
     return warm, free
 
 
-class DeviceArrayMooring:
+class DeviceArrayMooring(DeviceRecords):
     """One or more records resident on the device; poses and cases pick a record through sys_idx.
     Outputs are laid out for the largest record: nb = largest nbody, nl = largest nline, nf = largest
     nfree; T and J have 2 nl rows per pose (TA of line l in row l, TB in row nl + l); rows and columns
@@ -112,10 +113,8 @@ class DeviceArrayMooring:
 
     def __init__(self, records, device=0):
         self.records = [r if isinstance(r, ArrayRecord) else flatten_array(r) for r in records]   # refusals first
-        import torch
-        self.torch = torch
-        self.dev_index = device
-        self.device = torch.device(f"cuda:{device}")
+        super().__init__(device)
+        torch = self.torch
         self.nsys = len(self.records)
         self.nb = max(r.nbody for r in self.records)
         self.nl = max(r.nline for r in self.records)
@@ -130,8 +129,7 @@ class DeviceArrayMooring:
             a.g, a.rho, a.free_tol, a.free_depth = r.g, r.rho, r.free_tol, r.free_depth
             a.point, a.line = self._pt[i].data_ptr(), self._ln[i].data_ptr()
             a.point_host, a.line_host = r.point.ctypes.data, r.line.ctypes.data
-        raw = np.frombuffer(bytes(self._arr), dtype=np.uint8).copy()
-        self._arr_dev = torch.tensor(raw, dtype=torch.uint8, device=self.device)
+        self._arr_dev = self.upload(self._arr)
 
     def same_tables(self, records):
         """Whether `records` (ArrayRecord) hold exactly the tables and scalars resident on the device."""
@@ -141,22 +139,6 @@ class DeviceArrayMooring:
             and np.array_equal(a.point, b.point) and np.array_equal(a.line, b.line)
             for a, b in zip(records, self.records))
 
-    def _f64(self, x, shape):
-        t = self.torch.as_tensor(np.asarray(x, dtype=float) if not self.torch.is_tensor(x) else x,
-                                 dtype=self.torch.float64, device=self.device).contiguous()
-        if list(t.shape) != list(shape):
-            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
-        return t
-
-    def _idx(self, sys_idx, n):
-        """sys_idx is passed on as it is: an index outside [0, nsys) comes back as status 7."""
-        if sys_idx is None:
-            return None
-        idx = np.asarray(sys_idx, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError(f"sys_idx: {n} entries expected")
-        return self.torch.tensor(idx, dtype=self.torch.int32, device=self.device)
-
     def eval(self, r6, warm, free, sys_idx=None, jacobian=False):
         """rh_moor_array_eval at poses r6 [n, nb, 6] from the state warm [n, nl, 2] (or None: cold) and
         free [n, nf, 3].  Returns device tensors F [n, 6nb], K [n, 6nb, 6nb], T [n, 2nl], J [n, 2nl, 6nb]
@@ -165,11 +147,11 @@ class DeviceArrayMooring:
         torch = self.torch
         n = len(r6)
         nD = 6 * self.nb
-        r6 = self._f64(r6, [n, self.nb, 6])
+        r6 = self.f64(r6, [n, self.nb, 6])
         f64 = dict(dtype=torch.float64, device=self.device)
-        w = torch.zeros([n, self.nl, 2], **f64) if warm is None else self._f64(warm, [n, self.nl, 2]).clone()
-        fr = self._f64(free, [n, self.nf, 3]).clone()
-        idx = self._idx(sys_idx, n)
+        w = torch.zeros([n, self.nl, 2], **f64) if warm is None else self.f64(warm, [n, self.nl, 2]).clone()
+        fr = self.f64(free, [n, self.nf, 3]).clone()
+        idx = self.index(sys_idx, n)
         F = torch.zeros([n, nD], **f64)
         K = torch.zeros([n, nD, nD], **f64)
         T = torch.zeros([n, 2 * self.nl], **f64)
@@ -188,12 +170,12 @@ class DeviceArrayMooring:
         status [n]."""
         torch = self.torch
         n = len(X_ref)
-        X_ref = self._f64(X_ref, [n, self.nb, 6])
-        K_hs = self._f64(K_hs, [n, self.nb, 6, 6])
-        F_const = self._f64(F_const, [n, self.nb, 6])
-        w0 = None if warm0 is None else self._f64(warm0, [n, self.nl, 2])
-        f0 = self._f64(free0, [n, self.nf, 3])
-        idx = self._idx(sys_idx, n)
+        X_ref = self.f64(X_ref, [n, self.nb, 6])
+        K_hs = self.f64(K_hs, [n, self.nb, 6, 6])
+        F_const = self.f64(F_const, [n, self.nb, 6])
+        w0 = None if warm0 is None else self.f64(warm0, [n, self.nl, 2])
+        f0 = self.f64(free0, [n, self.nf, 3])
+        idx = self.index(sys_idx, n)
         f64 = dict(dtype=torch.float64, device=self.device)
         X = torch.zeros([n, 6 * self.nb], **f64)
         w = torch.zeros([n, self.nl, 2], **f64)

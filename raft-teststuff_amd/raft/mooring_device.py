@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from .device_records import DeviceRecords
 from .mooring import Point
 
 
@@ -51,17 +52,15 @@ def warm_state(ms):
     return np.array([[ln.HF, ln.VF] for ln in ms.lines], dtype=float)
 
 
-class DeviceMooring:
+class DeviceMooring(DeviceRecords):
     """One or more mooring systems resident on the device.  Poses and cases pick a system through
     sys_idx; the T and J outputs have 2 nl_max rows per pose: TA of line l in row l, TB in row
     nl_max + l (for a single system this is MooringSystem.tensions()' order)."""
 
     def __init__(self, systems, device=0):
         flat = [flatten(ms) for ms in systems]          # every refusal before the first device call
-        import torch
-        self.torch = torch
-        self.dev_index = device
-        self.device = torch.device(f"cuda:{device}")
+        super().__init__(device)
+        torch = self.torch
         self.nline = [t.shape[1] for t, _, _ in flat]
         self.nl_max = max(self.nline)
         self.nsys = len(flat)
@@ -71,33 +70,17 @@ class DeviceMooring:
             self._arr[i].nline, self._arr[i].pad_ = self.nline[i], 0
             self._arr[i].depth, self._arr[i].tol = depth, tol
             self._arr[i].line = self._tables[i].data_ptr()
-        raw = np.frombuffer(bytes(self._arr), dtype=np.uint8).copy()
-        self._arr_dev = torch.tensor(raw, dtype=torch.uint8, device=self.device)
-
-    def _f64(self, x, shape):
-        t = self.torch.as_tensor(np.asarray(x, dtype=float) if not self.torch.is_tensor(x) else x,
-                                 dtype=self.torch.float64, device=self.device).contiguous()
-        if list(t.shape) != list(shape):
-            raise ValueError(f"expected shape {list(shape)}, got {list(t.shape)}")
-        return t
-
-    def _idx(self, sys_idx, n):
-        if sys_idx is None:
-            return None
-        idx = np.asarray(sys_idx, dtype=np.int32)
-        if idx.shape != (n,) or (n and (idx.min() < 0 or idx.max() >= self.nsys)):
-            raise ValueError(f"sys_idx: {n} entries in [0, {self.nsys}) expected")
-        return self.torch.tensor(idx, dtype=self.torch.int32, device=self.device)
+        self._arr_dev = self.upload(self._arr)
 
     def eval(self, r6, sys_idx=None, warm=None, jacobian=False):
         """rh_moor_eval at poses r6 [n, 6].  warm [n, nl_max, 2] or None (cold).  Returns device
         tensors F [n,6], K [n,6,6], T [n,2 nl_max], J [n,2 nl_max,6] (or None), status [n], warm."""
         torch = self.torch
         n = len(r6)
-        r6 = self._f64(r6, [n, 6])
-        idx = self._idx(sys_idx, n)
+        r6 = self.f64(r6, [n, 6])
+        idx = self.index(sys_idx, n, limit=self.nsys)
         f64 = dict(dtype=torch.float64, device=self.device)
-        w = torch.zeros([n, self.nl_max, 2], **f64) if warm is None else self._f64(warm, [n, self.nl_max, 2]).clone()
+        w = torch.zeros([n, self.nl_max, 2], **f64) if warm is None else self.f64(warm, [n, self.nl_max, 2]).clone()
         F = torch.empty([n, 6], **f64)
         K = torch.empty([n, 6, 6], **f64)
         T = torch.empty([n, 2 * self.nl_max], **f64)
@@ -113,11 +96,11 @@ class DeviceMooring:
         Returns device tensors X [n,6], warm [n,nl_max,2], iters [n], status [n]."""
         torch = self.torch
         n = len(X_ref)
-        X_ref = self._f64(X_ref, [n, 6])
-        K_hs = self._f64(K_hs, [n, 6, 6])
-        F_const = self._f64(F_const, [n, 6])
-        w0 = None if warm0 is None else self._f64(warm0, [n, self.nl_max, 2])
-        idx = self._idx(sys_idx, n)
+        X_ref = self.f64(X_ref, [n, 6])
+        K_hs = self.f64(K_hs, [n, 6, 6])
+        F_const = self.f64(F_const, [n, 6])
+        w0 = None if warm0 is None else self.f64(warm0, [n, self.nl_max, 2])
+        idx = self.index(sys_idx, n, limit=self.nsys)
         f64 = dict(dtype=torch.float64, device=self.device)
         X = torch.empty([n, 6], **f64)
         w = torch.empty([n, self.nl_max, 2], **f64)

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _native as N
 from .ccblade import CCBlade, define_curvature
+from .device_records import DeviceRecords
 
 
 class FlatRotor:
@@ -154,15 +155,13 @@ def aero_param_row(rot, speed, mode):
     return row
 
 
-class DeviceRotor:
+class DeviceRotor(DeviceRecords):
     """One or more rotors resident on the device; operating points pick a rotor through rot_idx."""
 
     def __init__(self, rotors, device=0):
         self.flat = [r if isinstance(r, FlatRotor) else flatten_rotor(r) for r in rotors]   # refusals first
-        import torch
-        self.torch = torch
-        self.dev_index = device
-        self.device = torch.device(f"cuda:{device}")
+        super().__init__(device)
+        torch = self.torch
         self.nrot = len(self.flat)
         self.nr_max = max(f.nr for f in self.flat)
         self.ns_max = max(f.nsector for f in self.flat)
@@ -175,8 +174,7 @@ class DeviceRotor:
                     torch.tensor(f.coef, dtype=torch.float64, device=self.device).contiguous())
             self._tables.append(tabs)
             f.fill(self._arr[i], tabs)
-        raw = np.frombuffer(bytes(self._arr), dtype=np.uint8).copy()
-        self._arr_dev = torch.tensor(raw, dtype=torch.uint8, device=self.device)
+        self._arr_dev = self.upload(self._arr)
 
     def launch(self, rot_idx, op, derivatives=True, sections=False):
         """rh_rotor_loads at op [n, 5] = Uinf, Omega_rpm, pitch_deg, tilt, yaw.  rot_idx [n] (any
@@ -188,12 +186,7 @@ class DeviceRotor:
         n = op.shape[0]
         if list(op.shape) != [n, 5]:
             raise ValueError(f"expected op of shape [n, 5], got {list(op.shape)}")
-        idx = None
-        if rot_idx is not None:
-            idx = np.asarray(rot_idx, dtype=np.int32)
-            if idx.shape != (n,):
-                raise ValueError(f"rot_idx: {n} entries expected")
-            idx = torch.tensor(idx, dtype=torch.int32, device=self.device)
+        idx = self.index(rot_idx, n, name="rot_idx")
         f64 = dict(dtype=torch.float64, device=self.device)
         loads = torch.empty([n, 8], **f64)
         dloads = torch.empty([n, 2, 3], **f64) if derivatives else None

@@ -158,6 +158,18 @@ WIND = [dict(CASES["wind"]), dict(CASES["wind_wave_current"]),
 PARKED = dict(CASES["wind_wave_current"], wind_speed=30, turbine_status="parked")
 
 
+def count_launches(monkeypatch):
+    """Wraps DeviceRotor.launch (rh_rotor_loads) with a counter; returns the list it appends to."""
+    from raft.rotor_device import DeviceRotor
+    real, calls = DeviceRotor.launch, []
+
+    def counted(self, *a, **kw):
+        calls.append(1)
+        return real(self, *a, **kw)
+    monkeypatch.setattr(DeviceRotor, "launch", counted)
+    return calls
+
+
 def fresh(design):
     """A newly built model for each side of a comparison: the host path keeps the rotor's yaw from
     one case to the next (Rotor.setPosition takes the hub's lever arm with the yaw the last case
@@ -223,14 +235,17 @@ def test_statics_array_batch_with_device_rotor():
 
 
 @pytest.mark.parametrize("statics", [False, True], ids=["plain", "statics"])
-def test_analyze_cases_batch_with_device_rotor(statics):
+def test_analyze_cases_batch_with_device_rotor(statics, monkeypatch):
     """analyzeCasesBatch(rotor_device=True) against False: three wind cases and a parked one; identical
     drag iteration counts, Xi normwise at ten times the measured difference, the parked case's rows
-    bit-equal (no rotor load enters them)."""
+    bit-equal (no rotor load enters them).  The rotor loads of the whole call come from exactly one
+    launch, also with statics=True, where the statics and the per-pose designs share them."""
     cases = [copy.deepcopy(c) for c in (WIND[1], WIND[2], dict(WIND[3], wave_period=9, wave_height=3, wave_spectrum="JONSWAP",
                                                                 wave_heading=20), PARKED)]
     a = fresh("VolturnUS-S_aero").analyzeCasesBatch(cases, statics=statics, rotor_device=False)
+    launches = count_launches(monkeypatch)
     b = fresh("VolturnUS-S_aero").analyzeCasesBatch(cases, statics=statics, rotor_device=True)
+    assert len(launches) == 1, len(launches)
     assert np.array_equal(a["iters"], b["iters"]) and np.array_equal(a["status"], b["status"])
     worst = max(nrm(b["Xi"][i], a["Xi"][i]) for i in range(3))
     print(f"analyzeCasesBatch(statics={statics}): Xi normwise difference {worst:.2e}")
@@ -280,14 +295,17 @@ def test_invalid_records_are_refused_before_the_launch(rotors):
     assert launch()[3][0] == 0
 
 
-def test_analyze_array_batch_with_device_rotor():
+def test_analyze_array_batch_with_device_rotor(monkeypatch):
     """analyzeArrayBatch(statics=True, rotor_device=True) against False on VolturnUS-S_farm_aero, one case
     with a per-FOWT wind-speed list: equal statics and drag iteration counts, offsets within 1e-6 m and
-    1e-8 rad, Xi normwise at ten times the measured difference."""
+    1e-8 rad, Xi normwise at ten times the measured difference; exactly one rotor launch per FOWT."""
     waves = dict(wave_spectrum="JONSWAP", wave_period=10, wave_height=4, wave_heading=-30)
     cases = [dict(CASES["wind"], **waves), dict(CASES["wind_wave_current"], wind_speed=[10.0, 6.0])]
     a = fresh("VolturnUS-S_farm_aero").analyzeArrayBatch(cases, statics=True, rotor_device=False)
-    b = fresh("VolturnUS-S_farm_aero").analyzeArrayBatch(cases, statics=True, rotor_device=True)
+    launches = count_launches(monkeypatch)
+    farm = fresh("VolturnUS-S_farm_aero")
+    b = farm.analyzeArrayBatch(cases, statics=True, rotor_device=True)
+    assert len(launches) == farm.nFOWT == 2, len(launches)
     assert np.array_equal(a["iters"], b["iters"]) and np.array_equal(a["status"], b["status"])
     assert np.array_equal(a["statics_iters"], b["statics_iters"])
     assert not np.any(a["statics_status"]) and not np.any(b["statics_status"])
