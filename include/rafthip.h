@@ -453,6 +453,55 @@ int rh_rotor_aero_mb(rh_ctx* ctx, int ncase, int npair, int nw, const double* w,
                      const double* param, const double* M0, const double* B0, int base_per_bin, double* M, double* B,
                      double* f_aero0, rh_stream stream);
 
+/* ---- turbine output channels of batched cases (csrc/rh_channels.h, rh_channels.hip) ----
+ * The per-rotor channels FOWT.saveTurbineOutputs leaves in case_metrics (raft/fowt.py: rotor_channels,
+ * _aero_outputs), for every case of a batch in one launch: nacelle acceleration, tower-base bending
+ * moment and, for a pair with aeroServoMod 2, rotor speed [rpm], generator torque and blade pitch
+ * [deg] through the control transfer function of Rotor.calcAero; their PSDs, standard deviations and
+ * means, and the mean power.  The Kaimal spectrum is not covered: the host passes sqrt(S_rot). */
+enum rh_turbine_channel {
+  RH_TC_AXRNA = 0, RH_TC_MBASE, RH_TC_OMEGA, RH_TC_TORQUE, RH_TC_BPITCH,
+  RH_TC_SPECTRA = 5,           /* the channels above have a PSD and a standard deviation */
+  RH_TC_POWER = 5,             /* a mean only */
+  RH_TC_COUNT = 6
+};
+/* one row per (case, rotor) pair next to its rh_aero_param_field row: what the channels read and
+ * that row does not carry */
+enum rh_chan_pair_field {
+  RH_CP_ZHUB = 0,              /* rot.r3[2]: the hub height the floating feedback divides by */
+  RH_CP_KP_TAU, RH_CP_KI_TAU,  /* rot.kp_tau, rot.ki_tau as the torque channel reads them: not gated */
+  RH_CP_COUNT = 4              /* (one pad) */
+};
+/* one row per rotor of the FOWT, shared by all cases, as FOWT.rotor_channels forms the values */
+enum rh_chan_geom_field {
+  RH_CG_ZREL = 0,              /* rot.r_rel[2] */
+  RH_CG_MT, RH_CG_ZCG, RH_CG_HARM, RH_CG_ICG,   /* tower + RNA mass, its CG height, zCG - zBase, inertia about the CG */
+  RH_CG_G, RH_CG_ZBASE,
+  RH_CG_HAS_TOWER,             /* 0.0: a rotor index at or beyond the number of towers, no Mbase */
+  RH_CG_COUNT = 8
+};
+#define RH_CHAN_MAX_ROTORS 16 /* rotors of the FOWT */
+
+/* psd [ncase][nrot][RH_TC_SPECTRA][nw] (or NULL), stdv [ncase][nrot][RH_TC_SPECTRA] and avg
+ * [ncase][nrot][RH_TC_COUNT] (device).  w: device [nw]; Xi: device [ncase][nrow][6][nw], the response
+ * rows of every case (rows of zeros add nothing); pitch0: device [ncase], the mean pitch [rad], or
+ * NULL for zero; geom: device [nrot][RH_CG_COUNT].  The pair columns as rh_rotor_aero_mb takes them
+ * (pair_case non-decreasing, a case's pairs in rotor order, at most RH_AERO_MAX_PAIRS of them), each
+ * with its HOST copy, validated here before the launch; pair_rotor [npair] in [0, nrot), no rotor
+ * twice on a case; pair_mode_host HOST [npair], 1 or 2 (the kernel reads RH_AP_MODE of param).
+ * loads [npair][8], dloads [npair][2][3]: as rh_rotor_loads writes them; param
+ * [npair][RH_AP_COUNT]; op [npair][5]: rh_rotor_loads' operating points; pair_row
+ * [npair][RH_CP_COUNT]; pair_vw [npair] in [0, nvw): the pair's row of V_w, device [nvw][nw], the
+ * rotor-averaged turbulence amplitude sqrt(S_rot).  npair = 0 with NULL pair tables is a batch
+ * without wind.  A mode-2 pair's control channels gain one wind row of zero motion,
+ * phi = -C V_w / (i w); a rotor without a mode-2 pair on the case has zeros there. */
+int rh_turbine_channels(rh_ctx* ctx, int ncase, int nrow, int nw, double dw, const double* w, const rh_c128* Xi,
+                        const double* pitch0, int nrot, const double* geom, int npair, const int* pair_case,
+                        const int* pair_case_host, const int* pair_rotor, const int* pair_rotor_host,
+                        const int* pair_mode_host, const double* loads, const double* dloads, const double* param,
+                        const double* op, const double* pair_row, const int* pair_vw, const int* pair_vw_host, int nvw,
+                        const double* V_w, double* psd, double* stdv, double* avg, rh_stream stream);
+
 /* Drag-linearisation fixed point + per-bin Z assemble / pivoted LU solve for a batch of
  * cases, one workgroup per case.  Replaces Model.solveDynamics' per-FOWT iteration
  * (raft/raft_model.py:877-1013) including FOWT.calcHydroLinearization (raft/raft_fowt.py:

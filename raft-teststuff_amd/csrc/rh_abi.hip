@@ -382,6 +382,7 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
 #include "rh_moor_array.hip"   // k_moor_array_eval, k_array_statics_solve + their two ABI calls
 #include "rh_rotor.hip"        // k_rotor_loads + rh_rotor_loads
 #include "rh_aero.hip"         // k_rotor_aero_mb + rh_rotor_aero_mb
+#include "rh_channels.hip"     // k_turbine_channels + rh_turbine_channels
 extern "C" {
 
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,

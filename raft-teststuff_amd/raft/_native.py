@@ -120,6 +120,15 @@ AP = {"MODE": 0, "RQ": 1, "RHUB": 10, "I_DRIVETRAIN": 13, "NG": 14, "K_FLOAT": 1
       "KP_TAU": 18, "KI_TAU": 19, "GYRO": 20}
 AP_COUNT = 24
 AERO_MAX_PAIRS = 8
+# rh_turbine_channels: the channel order (enum rh_turbine_channel), the per-pair row (enum
+# rh_chan_pair_field), the per-rotor geometry row (enum rh_chan_geom_field) and the limit of rotors
+TC = {"AXRNA": 0, "MBASE": 1, "OMEGA": 2, "TORQUE": 3, "BPITCH": 4, "POWER": 5}
+TC_SPECTRA, TC_COUNT = 5, 6
+CP = {"ZHUB": 0, "KP_TAU": 1, "KI_TAU": 2}
+CP_COUNT = 4
+CG = {"ZREL": 0, "MT": 1, "ZCG": 2, "HARM": 3, "ICG": 4, "G": 5, "ZBASE": 6, "HAS_TOWER": 7}
+CG_COUNT = 8
+CHAN_MAX_ROTORS = 16
 
 
 class NativeError(RuntimeError):
@@ -165,6 +174,9 @@ def lib():
                                    _p],
                 "rh_rotor_aero_mb": [_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                      ctypes.c_int, _p, _p, _p, _p],
+                "rh_turbine_channels": [_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _p, _p, _p,
+                                        ctypes.c_int, _p, ctypes.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                        ctypes.c_int, _p, _p, _p, _p, _p],
                 "rh_solve_cases": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.POINTER(RhCases),
                                    ctypes.POINTER(RhSolveOut), _p],
                 "rh_heading_response": [_p, ctypes.POINTER(RhDesign), ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,

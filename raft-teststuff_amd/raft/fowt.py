@@ -375,7 +375,9 @@ class FOWT:
         gets them unchanged).  Only the status column is read back; a non-zero status raises the
         RuntimeError of rotorLoadsBatch.  Returns device tensors M [n, nw, 6, 6], B [n, nw, 6, 6]
         and f_aero0 [n, 6] (the mean aero load about the platform reference point, summed over the
-        case's rotors), or None when no rotor operates in any case.  What Rotor.calcAero also
+        case's rotors), or None when no rotor operates in any case; the dict also carries what the
+        launches left on the device for turbineChannelsBatch (loads, dloads, param, op) and the host
+        columns pair_case, modes and pairs [(case row, rotor)].  What Rotor.calcAero also
         forms, the wind excitation f_aero and the Kaimal spectrum, is not computed, and the FOWT's
         A_aero, B_aero, f_aero and B_gyro are left as they are.  Refused by name before any device
         call: underwater rotors, what flatten_rotor refuses, and an aeroServoMod other than 1 or 2
@@ -399,6 +401,85 @@ class FOWT:
         out = dr.aero_mb(res, len(cases), [ic for ic, _ in pairs], [modes[ir] for _, ir in pairs], param, base.w,
                          base.M, base.B)
         self._check_rotor_status(res, pairs, "aeroMBBatch")
+        out["pairs"] = pairs                          # (case row, rotor) of every pair, for turbineChannelsBatch
+        return out
+
+    def _channel_pair_tables(self, cases, mb, case_rows=None):
+        """The pair tables of rotor_device.turbine_channels from aeroMBBatch's result (None: no pairs),
+        the V_w table [nvw, nw] (row 0 zeros; one row per distinct (rotor, wind speed, turbulence) among
+        the pairs with aeroServoMod 2, Rotor.IECKaimal evaluated once for each) and, per case, the row of
+        its last such rotor (-1: none).  Host only."""
+        from .rotor_device import chan_pair_row
+        n = len(cases)
+        pairs = None
+        vw_rows, wind_row = [np.zeros(self.nw)], np.full(n, -1)
+        if mb is not None:
+            rows = np.arange(n) if case_rows is None else np.asarray(case_rows, dtype=np.int64)
+            keys, pair_vw, prow = {}, [], []
+            for (ic, ir), mode in zip(mb["pairs"], mb["modes"]):
+                rot, case = self.rnaList[ir], cases[rows[ic]]
+                prow.append(chan_pair_row(rot))
+                if mode != 2:
+                    pair_vw.append(0)
+                    continue
+                key = (ir, repr(case.get("wind_speed", 10.0)), repr(case.get("turbulence", 0.0)))
+                if key not in keys:
+                    keys[key] = len(vw_rows)
+                    vw_rows.append(np.sqrt(rot.IECKaimal(case)[3]))          # V_w as Rotor.calcAero forms it
+                pair_vw.append(keys[key])
+                wind_row[rows[ic]] = keys[key]
+            pairs = dict(pair_case=rows[np.asarray(mb["pair_case"], dtype=np.int64)], pair_rotor=[ir for _, ir in mb["pairs"]],
+                         modes=mb["modes"], pair_vw=pair_vw, loads=mb["loads"], dloads=mb["dloads"], param=mb["param"],
+                         op=mb["op"], pair_row=np.array(prow), V_w=np.array(vw_rows))
+        return pairs, np.array(vw_rows), wind_row
+
+    def turbineChannelsBatch(self, cases, Xi, mb, device=0, case_rows=None):
+        """The turbine output channels of every case of a batch in one rh_turbine_channels launch
+        (raft/rotor_device.py), on the stream the solve ran on: what saveTurbineOutputs leaves in
+        case_metrics for the rotors, from the batch's response.  Xi: device complex128 [n, 6, nw] or
+        [n, nrow, 6, nw] (rows of zeros add nothing); mb: the dict aeroMBBatch returned, or None for
+        a batch without an operating rotor.  case_rows: the row in `cases` of each case aeroMBBatch
+        was given (increasing), where that was a selection of them; None: all of them, in order.
+        The host forms the Kaimal amplitude sqrt(S_rot) of Rotor.IECKaimal once per distinct (rotor,
+        wind speed, turbulence) among the pairs with aeroServoMod 2.  Returns device tensors in the
+        reference's per-case layouts stacked over the cases: AxRNA_ / Mbase_ avg, std, max, min
+        [n, nrot] and PSD [n, nw, nrot]; omega_ avg, std, max, min, PSD; torque_ and bPitch_ avg, std,
+        PSD; power_avg; wind_PSD [n, nw] (0.5 V_w^2 / dw of the case's last rotor with aeroServoMod 2,
+        zeros for a case without one).  The platform's mean pitch is that of its current pose."""
+        import torch
+        from .rotor_device import chan_geom_table, turbine_channels
+        n, nr, nw = len(cases), self.nrotors, self.nw
+        dev = Xi.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        names = dict(AxRNA=N.TC["AXRNA"], Mbase=N.TC["MBASE"], omega=N.TC["OMEGA"], torque=N.TC["TORQUE"],
+                     bPitch=N.TC["BPITCH"])
+        if nr == 0:
+            out = {f"{k}_{s}": torch.zeros([n, 0], **f64) for k in names for s in ("avg", "std")}
+            out.update({f"{k}_PSD": torch.zeros([n, nw, 0], **f64) for k in names})
+            out.update({f"{k}_{s}": torch.zeros([n, 0], **f64) for k in ("AxRNA", "Mbase", "omega") for s in ("max", "min")})
+            out["power_avg"], out["wind_PSD"] = torch.zeros([n, 0], **f64), torch.zeros([n, nw], **f64)
+            return out
+        if not hasattr(self, "mtower"):
+            raise RuntimeError("turbineChannelsBatch needs the tower masses and inertias of calcStatics (as "
+                               "saveTurbineOutputs does): call calcStatics first")
+        pairs, vw_rows, wind_row = self._channel_pair_tables(cases, mb, case_rows)
+        dd = self.device_design()
+        pitch0 = np.full(n, float(self.r6[4]))
+        res = turbine_channels(torch, dev, dev.index if dev.index is not None else device, Xi, dd.w, self.dw,
+                               chan_geom_table(self), pitch0, pairs)
+        psd, std, avg = res["psd"], res["std"], res["avg"]
+        out = {}
+        for name, k in names.items():
+            out[f"{name}_avg"], out[f"{name}_std"] = avg[:, :, k], std[:, :, k]
+            out[f"{name}_PSD"] = psd[:, :, k, :].transpose(1, 2)             # [n, nw, nrot]
+        for name, m in (("AxRNA", 3), ("Mbase", 3), ("omega", 2)):
+            out[f"{name}_max"] = out[f"{name}_avg"] + m * out[f"{name}_std"]
+            out[f"{name}_min"] = out[f"{name}_avg"] - m * out[f"{name}_std"]
+        out["power_avg"] = avg[:, :, N.TC["POWER"]]
+        V = torch.tensor(vw_rows, **f64)
+        wind = 0.5 * V.abs() ** 2 / self.dw
+        sel = torch.tensor(np.where(wind_row < 0, 0, wind_row), dtype=torch.long, device=dev)
+        out["wind_PSD"] = wind.index_select(0, sel) * torch.tensor(wind_row >= 0, **f64)[:, None]
         return out
 
     def calcTurbineConstants(self, case, ptfm_pitch=0, bem=None):

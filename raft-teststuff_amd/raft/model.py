@@ -841,7 +841,7 @@ class Model:
         return self.results
 
     def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
-                          pose_chunk=32, rotor_device=False, aero_device=False):
+                          pose_chunk=32, rotor_device=False, aero_device=False, channels=False):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -878,7 +878,20 @@ class Model:
         for a case without aero).  The wind excitation and the Kaimal spectrum are not computed (the
         solve reads neither), and the FOWT's host attributes A_aero, B_aero, f_aero and B_gyro stay as
         the aero-free design sets them: all zeros.  With statics=True and on an array it raises
-        NotImplementedError.  The default changes nothing."""
+        NotImplementedError.  The default changes nothing.
+        channels=True (single FOWT, statics=False) adds the turbine output channels saveTurbineOutputs
+        leaves in case_metrics, from one rh_turbine_channels launch after the solve on its stream
+        (FOWT.turbineChannelsBatch): AxRNA_ and Mbase_ avg / std / max / min [n, nrot] and PSD
+        [n, nw, nrot], omega_ avg / std / max / min / PSD, torque_ and bPitch_ avg / std / PSD,
+        power_avg and wind_PSD [n, nw], over every sea state of a case.  A batch with an operating
+        rotor needs aero_device=True (the pair tensors live on the device only there); with
+        statics=True and on an array it raises NotImplementedError.  The default changes nothing."""
+        if channels and statics:
+            raise NotImplementedError("analyzeCasesBatch: channels=True with statics=True (the per-pose path keeps no "
+                                      "pair tensors on the device; use saveTurbineOutputs per case there)")
+        if channels and self.nFOWT != 1:
+            raise NotImplementedError("analyzeCasesBatch: channels=True on an array (analyzeArrayBatch forms no "
+                                      "turbine channels)")
         if aero_device and statics:
             raise NotImplementedError("analyzeCasesBatch: aero_device=True with statics=True (the per-pose path "
                                       "rebuilds a design per case; use rotor_device=True there)")
@@ -899,6 +912,10 @@ class Model:
         multi = len(cases) > 0 and nws.max() > 1
         want_fp = tuple(want) + (("Bmat", "B_drag") if multi else ())
         sel = [i for i, c in enumerate(cases) if self._operating_rotor(fowt, c)]
+        if channels and sel and not aero_device:
+            raise NotImplementedError("analyzeCasesBatch: channels=True on a batch with an operating rotor needs "
+                                      "aero_device=True (the rotor loads and parameter rows the channels read are kept "
+                                      "on the device only there)")
         if multi:  # every heading tabulated before the fixed point (its tables stay put)
             fowt.device_design().ensure_headings(np.concatenate([np.asarray(s[0], dtype=float) for s in seas]) * DEG2RAD)
         if sel:     # (a batch without an operating rotor leaves the turbine constants as they are)
@@ -932,6 +949,9 @@ class Model:
             if mb is not None:
                 f0[torch.tensor(sel, dtype=torch.long, device=base.device)] = mb["f_aero0"]
             res["f_aero0"] = f0
+        if channels:
+            res.update(fowt.turbineChannelsBatch(cases, res["Xi_waves"] if multi else res["Xi"], mb, self.device,
+                                                 case_rows=sel))
         return res.host() if host else res
 
     def _calc_bem_once(self):

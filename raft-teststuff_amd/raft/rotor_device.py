@@ -155,6 +155,90 @@ def aero_param_row(rot, speed, mode):
     return row
 
 
+def chan_pair_row(rot):
+    """The rh_turbine_channels row of one (case, rotor) pair next to its aero_param_row: the hub height
+    the floating feedback of Rotor.calcAero divides by, and the torque gains as FOWT._aero_outputs reads
+    them from the rotor (not gated by the pitch gains, unlike the parameter row's)."""
+    row = np.zeros(N.CP_COUNT)
+    row[N.CP["ZHUB"]], row[N.CP["KP_TAU"]], row[N.CP["KI_TAU"]] = rot.r3[2], rot.kp_tau, rot.ki_tau
+    return row
+
+
+def chan_geom_table(fowt):
+    """The per-rotor geometry table [nrotors, CG_COUNT] of rh_turbine_channels, each value formed as
+    FOWT.rotor_channels and FOWT._aero_outputs form it.  A rotor index at or beyond the number of
+    towers has no tower-base moment (HAS_TOWER 0)."""
+    from .fowt import translate_matrix_6to6
+    geom = np.zeros([fowt.nrotors, N.CG_COUNT])
+    for ir, rot in enumerate(fowt.rnaList):
+        geom[ir, N.CG["ZREL"]], geom[ir, N.CG["G"]] = rot.r_rel[2], fowt.g
+    for ir, rot in enumerate(fowt.rnaList[:len(fowt.mtower)]):
+        mt = fowt.mtower[ir] + rot.mRNA
+        zCG = (fowt.rCG_tow[ir][2] * fowt.mtower[ir] + rot.r_rel[2] * rot.mRNA) / mt
+        tower = fowt.memberList[fowt.nplatmems + ir]
+        zBase = tower.rA[2]
+        ICG = (translate_matrix_6to6(tower.M_struc, [0, 0, -zCG])[4, 4] + rot.mRNA * (rot.r_rel[2] - zCG) ** 2
+               + rot.IrRNA)
+        for k, v in (("MT", mt), ("ZCG", zCG), ("HARM", zCG - zBase), ("ICG", ICG), ("ZBASE", zBase), ("HAS_TOWER", 1.0)):
+            geom[ir, N.CG[k]] = v
+    return geom
+
+
+def turbine_channels(torch, device, dev_index, Xi, w, dw, geom, pitch0=None, pairs=None, psd=True):
+    """rh_turbine_channels on the current stream of `device`.  Xi: device complex128 [ncase, nrow, 6, nw]
+    (or [ncase, 6, nw]); w: device [nw]; geom [nrot, CG_COUNT] (chan_geom_table); pitch0 [ncase] or None.
+    pairs: None for a batch without wind, or a dict of the pair tables: pair_case, pair_rotor, modes,
+    pair_vw (host integers [npair]), loads, dloads, param, op (device tensors, as rh_rotor_loads and
+    DeviceRotor.aero_mb hold them), pair_row [npair, CP_COUNT] and V_w [nvw, nw] (host or device).
+    Returns device tensors psd [ncase, nrot, TC_SPECTRA, nw] (None with psd=False),
+    std [ncase, nrot, TC_SPECTRA] and avg [ncase, nrot, TC_COUNT]."""
+    f64 = dict(dtype=torch.float64, device=device)
+    i32 = dict(dtype=torch.int32, device=device)
+    if Xi.dim() == 3:
+        Xi = Xi[:, None]
+    Xi = Xi.contiguous()
+    ncase, nrow, ndof, nw = Xi.shape
+    if ndof != 6 or Xi.dtype != torch.complex128 or int(w.shape[0]) != nw:
+        raise ValueError(f"turbine_channels: Xi complex128 [ncase, nrow, 6, {int(w.shape[0])}] expected, got "
+                         f"{Xi.dtype} {list(Xi.shape)}")
+    geom = np.ascontiguousarray(geom, dtype=np.float64)
+    nrot = geom.shape[0]
+    if geom.shape != (nrot, N.CG_COUNT):
+        raise ValueError(f"turbine_channels: geom of shape [nrot, {N.CG_COUNT}] expected")
+    as_dev = lambda a: a.to(**f64).contiguous() if torch.is_tensor(a) else \
+        torch.tensor(np.ascontiguousarray(a, dtype=np.float64), **f64)                              # noqa: E731
+    geom_dev = as_dev(geom)
+    p0 = None if pitch0 is None else as_dev(pitch0)
+    if p0 is not None and tuple(p0.shape) != (ncase,):
+        raise ValueError("turbine_channels: one mean pitch per case expected")
+    npair, nvw, host, dev = 0, 0, [None] * 4, [None] * 9
+    if pairs is not None and len(pairs["pair_case"]):
+        host = [np.ascontiguousarray(pairs[k], dtype=np.int32) for k in ("pair_case", "pair_rotor", "modes", "pair_vw")]
+        npair = len(host[0])
+        V_w = as_dev(pairs["V_w"])
+        nvw = int(V_w.shape[0])
+        tabs = [as_dev(pairs[k]) for k in ("loads", "dloads", "param", "op", "pair_row")]
+        if tuple(tabs[1].shape) == (npair, 6):        # dloads as a flat row per pair
+            tabs[1] = tabs[1].reshape(npair, 2, 3)
+        want = [(npair, 8), (npair, 2, 3), (npair, N.AP_COUNT), (npair, 5), (npair, N.CP_COUNT)]
+        if any(h.shape != (npair,) for h in host) or any(tuple(t.shape) != s for t, s in zip(tabs, want)) \
+                or tuple(V_w.shape) != (nvw, nw):
+            raise ValueError("turbine_channels: one entry of every pair table per pair and V_w [nvw, nw] expected")
+        dev = [torch.tensor(host[0], **i32), torch.tensor(host[1], **i32), torch.tensor(host[3], **i32), *tabs, V_w]
+    out_psd = torch.empty([ncase, nrot, N.TC_SPECTRA, nw], **f64) if psd else None
+    out_std = torch.empty([ncase, nrot, N.TC_SPECTRA], **f64)
+    out_avg = torch.empty([ncase, nrot, N.TC_COUNT], **f64)
+    hp = lambda a: None if a is None else a.ctypes.data                                             # noqa: E731
+    pc_dev, pr_dev, pv_dev, loads, dloads, param, op, prow, V_w = dev
+    N.check(N.lib().rh_turbine_channels(N.context(dev_index), ncase, nrow, nw, float(dw), N.ptr(w), N.ptr(Xi), N.ptr(p0),
+                                        nrot, N.ptr(geom_dev), npair, N.ptr(pc_dev), hp(host[0]), N.ptr(pr_dev),
+                                        hp(host[1]), hp(host[2]), N.ptr(loads), N.ptr(dloads), N.ptr(param), N.ptr(op),
+                                        N.ptr(prow), N.ptr(pv_dev), hp(host[3]), nvw, N.ptr(V_w), N.ptr(out_psd),
+                                        N.ptr(out_std), N.ptr(out_avg), N.stream_handle(torch, device)),
+            "rh_turbine_channels")
+    return dict(psd=out_psd, std=out_std, avg=out_avg, _keep=(Xi, geom_dev, p0, dev))
+
+
 class DeviceRotor(DeviceRecords):
     """One or more rotors resident on the device; operating points pick a rotor through rot_idx."""
 
@@ -203,7 +287,9 @@ class DeviceRotor(DeviceRecords):
         (non-decreasing, the pairs of a case in rotor order), modes [npair] their aeroServoMod,
         param [npair, AP_COUNT] their rows (aero_param_row); w [nw], M0, B0 ([6, 6] or [nw, 6, 6])
         device tensors of the base design.  Returns device tensors M [ncase, nw, 6, 6],
-        B [ncase, nw, 6, 6] and f_aero0 [ncase, 6]."""
+        B [ncase, nw, 6, 6] and f_aero0 [ncase, 6], and with them the pair tables it holds on the
+        device (loads, dloads, param, op) and the host columns pair_case and modes, for
+        turbine_channels()."""
         torch = self.torch
         pc = np.ascontiguousarray(pair_case, dtype=np.int32)
         md = np.ascontiguousarray(modes, dtype=np.int32)
@@ -227,7 +313,12 @@ class DeviceRotor(DeviceRecords):
                                          pc.ctypes.data, md.ctypes.data, N.ptr(res["loads"]), N.ptr(res["dloads"]),
                                          N.ptr(par_dev), N.ptr(M0), N.ptr(B0), int(per_bin), N.ptr(M), N.ptr(B),
                                          N.ptr(f0), N.stream_handle(torch, self.device)), "rh_rotor_aero_mb")
-        return dict(M=M, B=B, f_aero0=f0, _keep=(pc_dev, par_dev, res))
+        return dict(M=M, B=B, f_aero0=f0, loads=res["loads"], dloads=res["dloads"], param=par_dev, op=res["_keep"][0],
+                    pair_case=pc, modes=md, _keep=(pc_dev, par_dev, res))
+
+    def turbine_channels(self, Xi, w, dw, geom, pitch0=None, pairs=None, psd=True):
+        """rh_turbine_channels on the stream of launch() and aero_mb(): see turbine_channels()."""
+        return turbine_channels(self.torch, self.device, self.dev_index, Xi, w, dw, geom, pitch0, pairs, psd)
 
     def evaluate(self, rot_idx, Uinf, Omega_rpm, pitch_deg, tilt, yaw, derivatives=True, sections=False):
         """CCBlade.evaluate of every operating point (tilt and yaw [rad] as Rotor.runCCBlade sets
