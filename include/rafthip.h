@@ -197,7 +197,8 @@ int rh_set_qtf_path(rh_ctx* ctx, int path);
  *   finer[h][:,b]    = sum_n translateForce3to6DOF(Imat_n(b) iw uhat + pDyn a_i q, r_n)
  *   kproj[h][n][:,b] = (q.uhat, p1.uhat, p2.uhat) of node n (the only form the drag loop needs)
  * so that for a sea state with amplitudes zeta(b): u = zeta*uhat, F_hydro_iner = zeta*finer.
- * beta: device [nhead] (rad).  Outputs are device buffers sized as in rh_design. */
+ * beta: device [nhead] (rad).  Outputs are device buffers sized as in rh_design.  A one-bin grid
+ * (nw = 1) is accepted here; the solve entry points need nw >= 2. */
 int rh_wave_tables(rh_ctx* ctx, const rh_design* d, const double* beta,
                    rh_c128* uhat, rh_c128* finer, rh_c128* kproj, rh_stream stream);
 

@@ -91,8 +91,9 @@ constexpr size_t kMaxLds = 160 * 1024;   // LDS per workgroup on gfx950
 
 // need_uhat: the entry point's kernels read the velocity table (the fixed point does not: it
 // reads kproj and finer only, so a sweep block may skip uhat, rh_wave_tables_batch)
-int check_design(const rh_design& d, bool need_tables, bool need_uhat = true) {
-  if (d.nw < 2 || d.nw > 2048) return fail(RH_EINVAL, "nw=%d outside [2, 2048]", d.nw);
+// min_nw: 1 for rh_wave_tables, whose kernels need no second bin (dw is a field of its own)
+int check_design(const rh_design& d, bool need_tables, bool need_uhat = true, int min_nw = 2) {
+  if (d.nw < min_nw || d.nw > 2048) return fail(RH_EINVAL, "nw=%d outside [%d, 2048]", d.nw, min_nw);
   if (d.nn < 0 || d.nn > kMaxNodes) return fail(RH_EINVAL, "nn=%d outside [0, %d]", d.nn, kMaxNodes);
   if (!d.w || !d.k || (d.nn > 0 && !d.node)) return fail(RH_EINVAL, "design: null w/k/node table");
   if (!d.M || !d.B || !d.C) return fail(RH_EINVAL, "design: null M/B/C");
@@ -264,7 +265,7 @@ int rh_ctx_destroy(rh_ctx* ctx) {
 int rh_wave_tables(rh_ctx* ctx, const rh_design* d, const double* beta, rh_c128* uhat, rh_c128* finer,
                    rh_c128* kproj, rh_stream stream) {
   if (!ctx || !d || !beta || !uhat || !finer || !kproj) return fail(RH_EINVAL, "rh_wave_tables: null argument");
-  if (int r = check_design(*d, false)) return r;
+  if (int r = check_design(*d, false, true, 1)) return r;
   if (d->nhead < 1) return fail(RH_EINVAL, "rh_wave_tables: nhead must be >= 1");
   RH_HIP(hipSetDevice(ctx->device));
   const hipStream_t s = (hipStream_t)stream;
