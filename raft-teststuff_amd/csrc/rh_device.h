@@ -52,10 +52,14 @@ RH_DEV double cabs1(cd a) { return fabs(a.r) + fabs(a.i); }  // LAPACK dcabs1
 RH_DEV cd msub(cd a, cd l, cd u) {
   return cd{__builtin_fma(l.i, u.i, __builtin_fma(-l.r, u.r, a.r)), __builtin_fma(-l.i, u.r, __builtin_fma(-l.r, u.i, a.i))};
 }
-// does any lane of the wave hold p (the host build has one lane)
+// does any lane of the wave hold p (the host build has one lane; with RH_HOST_WAVE_ANY_TRUE it answers as
+// a lane whose wave mates always hold p, so every block guarded by it is entered: tools/lu_rows_host.cpp)
 RH_DEV bool wave_any(bool p) {
 #if defined(__HIPCC__)
   return __builtin_amdgcn_ballot_w64(p) != 0;
+#elif defined(RH_HOST_WAVE_ANY_TRUE)
+  (void)p;
+  return true;
 #else
   return p;
 #endif
@@ -74,7 +78,10 @@ RH_DEV cd cdiv(cd a, cd b) {
 // In-register Gaussian elimination with partial pivoting (max |re|+|im|, first maximum
 // wins as in izamax) on an N x N complex system; A and x are overwritten, x = A^-1 x.
 // Returns false on an exactly zero pivot (LAPACK: info > 0 -> LinAlgError("Singular matrix")).
-template <int N>
+// ROWS picks the form of the row exchange (the same bits either way): true, one uniform test per
+// candidate row; false, one test per step around a select chain over every candidate row, the form
+// before it, kept for k_solve_cases<2> and <8>, which spill more with the per-row form.
+template <int N, bool ROWS = true>
 RH_DEV bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
   bool ok = true;
 #pragma unroll
@@ -87,22 +94,28 @@ RH_DEV bool lu_solve(cd (&A)[N][N], cd (&x)[N]) {
       if (v > best) { best = v; p = i; }
     }
     ok = ok && (best != 0.0);
-    // The row exchange is a chain of per-lane selects; skip it when no lane of the wave
-    // pivots off the diagonal at this step (the common case for these impedance matrices).
-    // Results are the same either way.
-    if (wave_any(p != k)) {
+    // The row exchange is per-lane selects between row k and each candidate row i, entered only for
+    // the rows some lane of the wave pivots to (one uniform test per row).  A lane with p != i
+    // selects what it holds, so entering a row's block or not leaves every lane's bits alone.  With
+    // these impedance matrices a step's lanes mostly agree on one off-diagonal row (surge pivots to
+    // the pitch row and sway to the roll row, whose coupling entries exceed the diagonal: DESIGN.md
+    // §5, "The LU's row exchange"), so one block runs where a chain over all rows k+1 .. N-1 did.
+    // (!ROWS: the chain, skipped only when no lane of the wave pivots off the diagonal at this step.)
+    if (ROWS || wave_any(p != k)) {
 #pragma unroll
       for (int i = k + 1; i < N; ++i) {
         const bool sw = (p == i);
+        if (!ROWS || wave_any(sw)) {
 #pragma unroll
-        for (int j = k; j < N; ++j) {
-          const cd a = A[k][j], b = A[i][j];
-          A[k][j] = sw ? b : a;
-          A[i][j] = sw ? a : b;
+          for (int j = k; j < N; ++j) {
+            const cd a = A[k][j], b = A[i][j];
+            A[k][j] = sw ? b : a;
+            A[i][j] = sw ? a : b;
+          }
+          const cd a = x[k], b = x[i];
+          x[k] = sw ? b : a;
+          x[i] = sw ? a : b;
         }
-        const cd a = x[k], b = x[i];
-        x[k] = sw ? b : a;
-        x[i] = sw ? a : b;
       }
     }
     // 1/piv = conj(piv) / |piv|^2: one real division per pivot, reused by the back

@@ -405,7 +405,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_solve_cases(CaseArgs a) {
 #pragma unroll
         for (int e = 0; e < 36; ++e) st(Zo + e, Z[e / 6][e % 6]);
       }
-      const bool ok_lu = lu_solve<6>(Z, F);
+      // the per-row exchange where it costs no register: with it NB = 2 spills 63 VGPRs for 61 and
+      // NB = 8 496 for 490 (tools/isa_check.py), so those two keep the chain (the same bits)
+      const bool ok_lu = lu_solve<6, NB == 1 || NB == 4>(Z, F);
       my_sing |= okb && !ok_lu;
 #pragma unroll
       for (int c = 0; c < 6; ++c) {
