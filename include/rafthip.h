@@ -374,6 +374,58 @@ int rh_array_statics_solve(rh_ctx* ctx, const rh_moor_array_system* sys, const r
                            const double* warm0, const double* free0, double* X, double* warm, double* free_pts,
                            int* iters, int* status, rh_stream stream);
 
+/* ---- per-pose strip tables and current loads (csrc/rh_pose.h, rh_pose.hip) ----
+ * The device form of what a new platform pose changes in a FOWT's design tables (Member.setPosition
+ * and the pose-dependent columns of prep.node_table), and of FOWT.calcCurrentLoads for many cases.
+ * The record is built once per FOWT at its reference pose (raft/pose_device.py): the members at the
+ * zero pose and, for ALL strip nodes (dry ones included, reference member/node order), a node table
+ * whose rows RH_NF_AQ .. RH_NF_T hold the columns that do not change with the pose (Imat and a_i of
+ * calcHydroConstants at the reference pose: a node that is dry there keeps its zeros when a pose
+ * wets it, as on the host; RH_NF_MCF = 0: MacCamy-Fuchs members are refused).  Rows RH_NF_RX ..
+ * RH_NF_P2Z of the record are not read. */
+enum rh_pose_member_field {
+  RH_PM_RA0X, RH_PM_RA0Y, RH_PM_RA0Z, /* end A at the zero pose [m] */
+  RH_PM_RB0X, RH_PM_RB0Y, RH_PM_RB0Z, /* end B */
+  RH_PM_L,                            /* member length [m] */
+  RH_PM_Q0X, RH_PM_Q0Y, RH_PM_Q0Z,    /* q, p1, p2 as Member.setPosition forms them before Rp is applied */
+  RH_PM_P10X, RH_PM_P10Y, RH_PM_P10Z,
+  RH_PM_P20X, RH_PM_P20Y, RH_PM_P20Z,
+  RH_PM_COUNT
+};
+#define RH_POSE_MAX_MEMBERS 256
+#define RH_POSE_MAX_NODES 1024
+
+typedef struct {
+  int nmemb, nnode;
+  const double* memb;      /* device [RH_PM_COUNT][nmemb], struct of arrays */
+  const double* node;      /* device [RH_NF_COUNT][nnode] */
+  const int* mstart;       /* device [nmemb+1]: first node of each member, mstart[nmemb] = nnode */
+  const int* mstart_host;  /* the same table in host memory: validated before the launch */
+} rh_pose_record;
+
+/* The design tables of npose poses X [npose][6] (device) in ONE launch, one workgroup per pose.  For
+ * pose i, into slabs of capacity RH_NF_COUNT nnode, RH_MF_COUNT nmemb and nmemb + 1:
+ *   node_out + i RH_NF_COUNT nnode : the compact [RH_NF_COUNT][nn_i] node table (field stride nn_i)
+ *   memb_out + i RH_MF_COUNT nmemb : the [RH_MF_COUNT][nm_i] member table (field stride nm_i)
+ *   mstart_out + i (nmemb + 1)     : mstart [nm_i + 1]
+ *   nn_out[i], nm_out[i]           : the submerged nodes and the members that keep one
+ * exactly what prep.node_table gives after FOWT.setPosition(X_i): Rp = rotation_matrix(X[3:]), rA =
+ * X[:3] + Rp rA0 (rB alike), r = rA + (ls / l)(rB - rA), q, p1, p2 = Rp (zero-pose vectors), a node
+ * kept iff r_z < 0.  A slab's entries past its table are not written. */
+int rh_pose_designs(rh_ctx* ctx, const rh_pose_record* rec, int npose, const double* X, double* node_out,
+                    double* memb_out, int* mstart_out, int* nn_out, int* nm_out, rh_stream stream);
+
+/* FOWT.calcCurrentLoads of ncase cases at the pose X_ref (HOST [6], a pure translation: X_ref[3:] = 0,
+ * so the record's zero-pose vectors are the pose's): the mean Morison drag of a uniform current with
+ * a power-law profile speed ((depth - |z|) / (depth + Zref))^shearExp on every node with r_z < 0
+ * (circular members take |vp| for both transverse norms, rectangular ones |vp1| and |vp2|), as forces
+ * and moments about X_ref[:3].  speed, heading_deg: device [ncase]; D_out: device [ncase][6].  One
+ * wave per case, the nodes over its lanes, a fixed-order butterfly: a case's bits do not depend on
+ * the other cases of the call. */
+int rh_current_loads(rh_ctx* ctx, const rh_pose_record* rec, const double* X_ref, int ncase, const double* speed,
+                     const double* heading_deg, double depth, double Zref, double shearExp, double rho, double* D_out,
+                     rh_stream stream);
+
 /* ---- rotor blade-element momentum loads (csrc/rh_rotor.h, rh_rotor.hip) ----
  * The device form of raft/ccblade.py's CCBlade.evaluate (iterRe = 1, airfoils with one Reynolds
  * number): one workgroup per operating point, one lane per (sector, section); the sections of a

@@ -384,6 +384,7 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
 #include "rh_rotor.hip"        // k_rotor_loads + rh_rotor_loads
 #include "rh_aero.hip"         // k_rotor_aero_mb + rh_rotor_aero_mb
 #include "rh_channels.hip"     // k_turbine_channels + rh_turbine_channels
+#include "rh_pose.hip"         // k_pose_designs, k_current_loads + rh_pose_designs, rh_current_loads
 extern "C" {
 
 int rh_solve_cases(rh_ctx* ctx, const rh_design* designs, int ndesign, const rh_cases* cases,

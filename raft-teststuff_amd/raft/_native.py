@@ -88,6 +88,18 @@ class RhMoorArraySystem(ctypes.Structure):
                 ("point_host", _p), ("line_host", _p)]
 
 
+class RhPoseRecord(ctypes.Structure):
+    _fields_ = [("nmemb", ctypes.c_int), ("nnode", ctypes.c_int), ("memb", _p), ("node", _p), ("mstart", _p),
+                ("mstart_host", _p)]
+
+
+# member-table row order of rh_pose_record (enum rh_pose_member_field) and the limits of its two calls
+POSE_MEMBER_FIELDS = ["RA0X", "RA0Y", "RA0Z", "RB0X", "RB0Y", "RB0Z", "L", "Q0X", "Q0Y", "Q0Z", "P10X", "P10Y", "P10Z",
+                      "P20X", "P20Y", "P20Z"]
+PM_COUNT = len(POSE_MEMBER_FIELDS)
+POSE_MAX_MEMBERS, POSE_MAX_NODES = 256, 1024
+
+
 # point-table and line-table row order of a general system (enum rh_moor_point_field, rh_moor_aline_field)
 MOOR_POINT_FIELDS = ["KIND", "INDEX", "X", "Y", "Z", "M", "V"]
 MP = {name: i for i, name in enumerate(MOOR_POINT_FIELDS)}
@@ -170,6 +182,9 @@ def lib():
                                        _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_array_statics_solve": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p,
                                            _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+                "rh_pose_designs": [_p, ctypes.POINTER(RhPoseRecord), ctypes.c_int, _p, _p, _p, _p, _p, _p, _p],
+                "rh_current_loads": [_p, ctypes.POINTER(RhPoseRecord), _p, ctypes.c_int, _p, _p, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _p],
                 "rh_rotor_loads": [_p, ctypes.POINTER(RhRotor), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p,
                                    _p],
                 "rh_rotor_aero_mb": [_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p,

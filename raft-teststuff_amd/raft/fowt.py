@@ -54,6 +54,7 @@ class FOWT:
     def __getstate__(self):
         st = dict(self.__dict__)
         st["_dd"] = None          # device buffers never travel (host tables do)
+        st.pop("_pose_dev", None)
         for k, v in st.items():
             if isinstance(v, np.ndarray) and v.size > 4096 and not v.any():
                 st[k] = _Zeros(v)
@@ -286,6 +287,27 @@ class FOWT:
                 D[3:] += np.cross(r, f)
         self.D_hydro = D
         return D
+
+    def _current_zref(self):
+        """calcCurrentLoads' reference depth of the profile: the hub of an underwater rotor, else 0."""
+        Zref = 0.0
+        for rot in self.rnaList:
+            if rot.r3[2] < 0:
+                Zref = rot.r3[2]
+        return Zref
+
+    def currentLoadsBatch(self, cases, device=0):
+        """calcCurrentLoads of every case at the FOWT's current pose (a pure translation: the reference
+        pose) in one rh_current_loads launch (raft/pose_device.py): D [n, 6], forces and moments about
+        the PRP.  D_hydro is left as it is."""
+        from .pose_device import pose_record
+        speed = [get_from_dict(c, "current_speed", shape=0, default=0.0) for c in cases]
+        heading = [get_from_dict(c, "current_heading", shape=0, default=0) for c in cases]
+        rec = pose_record(self, device)
+        if not len(cases):
+            return np.zeros([0, 6])
+        return rec.current_loads(self.r6, speed, heading, self.depth, self._current_zref(), self.shearExp_water,
+                                 self.rho_water).cpu().numpy()
 
     def _rotor_operates(self, ir, case):
         """Whether calcTurbineConstants evaluates rotor ir's aerodynamics in this case."""

@@ -138,8 +138,9 @@ class Member:
         self.r = np.zeros([self.ns, 3])
 
     # -- pose (raft/raft_member.py:245-304) --------------------------------------------
-    def setPosition(self, r6=np.zeros(6)):
-        r6 = np.asarray(r6, dtype=float)
+    def zero_pose_frame(self):
+        """R and the unit vectors q, p1, p2 at the zero pose: what setPosition rotates by Rp (and the
+        member rows of the device pose record, raft/pose_device.py)."""
         rAB = self.rB0 - self.rA0
         q = rAB / np.linalg.norm(rAB)
         beta = np.arctan2(q[1], q[0])
@@ -152,6 +153,11 @@ class Member:
                       [-c3 * s2, s2 * s3, c2]])
         p1 = R @ np.array([1, 0, 0])
         p2 = np.cross(q, p1)
+        return R, q, p1, p2
+
+    def setPosition(self, r6=np.zeros(6)):
+        r6 = np.asarray(r6, dtype=float)
+        R, q, p1, p2 = self.zero_pose_frame()
         Rp = rotation_matrix(*r6[3:])
         self.R = Rp @ R
         self.q, self.p1, self.p2 = Rp @ q, Rp @ p1, Rp @ p2

@@ -413,26 +413,32 @@ class Model:
         return [fowt.rotorLoadsBatch([self._fowt_case(c, i) for c in cases], self.device)
                 for i, fowt in enumerate(self.fowtList)]
 
-    def _mean_loads(self, cases, F_und, bems=None):
+    def _mean_loads(self, cases, F_und, bems=None, D_cur=None):
         """F_const [n, nFOWT, 6] = F_und [nFOWT, 6] + F_env of every (case, FOWT) at the FOWTs' current
         poses, F_env built as solveStatics builds it: the mean aero loads (bems[FOWT][case]: the rotors'
-        loads from the device, else the host evaluates), current drag and the mean wave drift."""
+        loads from the device, else the host evaluates), current drag (D_cur[FOWT][case]: from the device,
+        FOWT.currentLoadsBatch, else calcCurrentLoads per case) and the mean wave drift."""
         F_const = np.zeros([len(cases), self.nFOWT, 6])
         for ic, case in enumerate(cases):
             for i, fowt in enumerate(self.fowtList):
                 ci = self._fowt_case(case, i)
                 fowt.calcTurbineConstants(ci, ptfm_pitch=0, bem=bems[i][ic] if bems else None)
-                F_env = np.sum(fowt.f_aero0, axis=1) + fowt.calcCurrentLoads(ci)
+                if D_cur is not None:
+                    fowt.D_hydro = D_cur[i][ic].copy()       # (where calcCurrentLoads leaves it)
+                else:
+                    fowt.calcCurrentLoads(ci)
+                F_env = np.sum(fowt.f_aero0, axis=1) + fowt.D_hydro
                 if getattr(fowt, "Fhydro_2nd_mean", None) is not None:
                     F_env = F_env + np.sum(fowt.Fhydro_2nd_mean, axis=0)
                 F_const[ic, i] = F_und[i] + F_env
         return F_const
 
-    def _statics_batch_inputs(self, cases, F_extra=None, bems=None):
+    def _statics_batch_inputs(self, cases, F_extra=None, bems=None, current_device=False):
         """The host side of solveStaticsBatch: the device mooring system, X_ref [6], K_hs [6,6],
         F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref.
         bems: None (the host evaluates the rotors), or a list, filled here after every refusal with the
-        rotors' device loads at X_ref (_array_rotor_loads) for the caller that needs them again."""
+        rotors' device loads at X_ref (_array_rotor_loads) for the caller that needs them again.
+        current_device: the current loads of all cases from one launch (FOWT.currentLoadsBatch at X_ref)."""
         from .mooring_device import DeviceMooring, warm_state
         if self.nFOWT != 1 or self.ms is not None:
             raise NotImplementedError("solveStaticsBatch: a single FOWT with its own mooring system (arrays and "
@@ -454,12 +460,13 @@ class Model:
         warm0 = warm_state(fowt.ms)                      # the line solutions at the reference pose
         if bems is not None:
             bems[:] = self._array_rotor_loads(cases)
-        F_const = self._mean_loads(cases, [fowt.W_struc + fowt.W_hydro], bems)[:, 0]
+        D_cur = [fowt.currentLoadsBatch([self._fowt_case(c, 0) for c in cases], self.device)] if current_device else None
+        F_const = self._mean_loads(cases, [fowt.W_struc + fowt.W_hydro], bems, D_cur)[:, 0]
         if F_extra is not None:
             F_const += np.asarray(F_extra, dtype=float).reshape(len(cases), 6)
         return dm, X_ref, K_hs, F_const, warm0
 
-    def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False):
+    def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False, current_device=False):
         """The mean offsets of many load cases in two device launches (rh_statics_solve, then
         rh_moor_eval at the solved poses): solveStatics' Newton per case, every case's lines in
         adjacent lanes (csrc/rh_moor.hip).  A single FOWT with its own mooring system; F_extra
@@ -469,12 +476,15 @@ class Model:
         path) and status [n] (0 = converged, else _native.MOOR_STATUS); numpy arrays, or device
         tensors with host=False.  The model is left at its reference pose.  rotor_device=True takes the
         rotors' blade-element loads of all cases from one device launch (FOWT.rotorLoadsBatch) instead of
-        one host CCBlade evaluation per case; a case whose rotor solve fails raises RuntimeError."""
-        return self._solve_statics_batch(cases, F_extra, host, [] if rotor_device else None)
+        one host CCBlade evaluation per case; a case whose rotor solve fails raises RuntimeError.
+        current_device=True takes the current loads of all cases from one rh_current_loads launch
+        (FOWT.currentLoadsBatch) instead of one calcCurrentLoads per case; the rest of the environmental
+        loads is unchanged.  The defaults change nothing."""
+        return self._solve_statics_batch(cases, F_extra, host, [] if rotor_device else None, current_device)
 
-    def _solve_statics_batch(self, cases, F_extra, host, bems):
+    def _solve_statics_batch(self, cases, F_extra, host, bems, current_device=False):
         """solveStaticsBatch with the rotor loads as _statics_batch_inputs takes them."""
-        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, bems)
+        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, bems, current_device)
         n = len(cases)
         sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)))
         ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True)
@@ -658,23 +668,90 @@ class Model:
         a2 = torch.matmul(J, Xi.real.contiguous()) ** 2 + torch.matmul(J, Xi.imag.contiguous()) ** 2   # [n, 2L, nw]
         return 0.5 * a2 / float(self.w[0]), torch.sqrt(0.5 * a2.sum(dim=2))
 
-    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False):
+    def _pose_device_chunks(self, fowt, cases, seas, sb, bems, tol, want, pose_chunk):
+        """The drag fixed points of analyzeCasesBatch(statics=True, pose_device=True): every chunk of
+        pose_chunk cases through PoseRecord.designs (the poses' node and member tables and wave tables
+        from two launches) and one solve_batch.  The FOWT stays at its reference pose, where the turbine
+        and hydro constants are taken; cases without an operating rotor share one M and B, a case with
+        one gets its own per-bin pair (CaseMB.of_case's) from the host."""
+        import torch
+        from .pose_device import pose_record
+        from .prep import linear_matrices
+        n = len(cases)
+        dev = sb["X"].device
+        f64 = dict(dtype=torch.float64, device=dev)
+        X_ref = self._reference_poses()[0]
+        if n:      # the aero-free design
+            fowt.calcTurbineConstants(dict(self._fowt_case(cases[0], 0), wind_speed=0.0), ptfm_pitch=0)
+        fowt.calcHydroConstants()
+        rec = pose_record(fowt, self.device)
+
+        def mb_of():
+            M, B, _, per_bin = linear_matrices(fowt)
+            return torch.tensor(M, **f64).contiguous(), torch.tensor(B, **f64).contiguous(), per_bin
+        shared = mb_of()
+        # C_lin of every case: prep.linear_matrices' (C_struc + C_moor) + C_hydro with the case's own C_moor
+        C = ((torch.tensor(fowt.C_struc, **f64) + sb["C_moor"]) + torch.tensor(fowt.C_hydro, **f64)).contiguous()
+        parts = []
+        for c0 in range(0, n, int(pose_chunk)):
+            ids = list(range(c0, min(n, c0 + int(pose_chunk))))
+            rows = []
+            for i in ids:
+                ci = self._fowt_case(cases[i], 0)
+                if any(fowt._rotor_operates(ir, ci) for ir in range(fowt.nrotors)):
+                    # the rotors' part of setPosition(X_ref), as the per-case path runs it ahead of the turbine
+                    # constants: the hub offsets follow the yaw the previous evaluation left (Rotor.setYaw)
+                    for rot in fowt.rnaList:
+                        rot.setPosition(X_ref)
+                    fowt.calcTurbineConstants(dict(ci), ptfm_pitch=0, bem=bems[0][i] if bems else None)
+                    rows.append(mb_of())
+                else:
+                    rows.append(shared)
+            hd, sp, Hs, Tp, gm = ([seas[i][k][0] for i in ids] for k in range(5))
+            blk = rec.designs(sb["X"][ids[0]:ids[-1] + 1], C[ids[0]:ids[-1] + 1], rows,
+                              np.asarray(hd, dtype=float) * DEG2RAD, self.nIter, self.XiStart)
+            cs = CaseSet(np.arange(len(ids), dtype=np.int32), hd, sp, Hs, Tp, gm)
+            res = solve_batch(blk, cs, self.nIter, self.XiStart, tol, want=tuple(want), prepared=rec.case_columns(cs))
+            parts.append({k: v.clone() for k, v in res.items()})
+            torch.cuda.synchronize(dev)                  # the chunk's tables are released below
+            del res, blk
+        if n:      # the turbine constants of the last case and the rotors at X_ref, as the per-case path leaves them
+            if rows[-1] is shared:
+                fowt.calcTurbineConstants(dict(self._fowt_case(cases[-1], 0)), ptfm_pitch=0)
+            for rot in fowt.rnaList:
+                rot.setPosition(X_ref)
+        fowt._dd = fowt._host = None
+        return parts
+
+    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False, pose_device=False):
         """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
         analyzeCases solves it when the mooring is a system.  Offsets, C_moor and the tension
         Jacobian of every case come from solveStaticsBatch; each case then gets its own
         DeviceDesign (the FOWT moved to its pose exactly as solveStatics leaves it: turbine and
         hydro constants at the reference pose, members and rotors at the offset pose, C_moor from
-        the device), and the drag fixed points run in chunks of pose_chunk views."""
+        the device), and the drag fixed points run in chunks of pose_chunk views.  pose_device: the
+        current loads of the statics and every chunk's designs from the device (_pose_device_chunks)."""
         import torch
         if self.nFOWT != 1 or self.ms is not None:
             raise NotImplementedError("analyzeCasesBatch(statics=True): arrays (their statics couple the FOWTs; "
                                       "use analyzeCases)")
         fowt = self.fowtList[0]
+        if pose_device:
+            from .pose_device import MCF_REFUSAL, host_record
+            if any(mem.MCF for mem in fowt.memberList):
+                raise NotImplementedError("analyzeCasesBatch(pose_device=True): " + MCF_REFUSAL)
+            if fowt.bem_excitation():
+                raise NotImplementedError("analyzeCasesBatch(pose_device=True): a design with BEM excitation (its "
+                                          "potential-flow tables are tabulated per design; use pose_device=False)")
+            host_record(fowt)                            # (the kernels' member and node limits)
         seas = self._refuse_pose_analysis("analyzeCasesBatch", cases, pose_chunk)
         self._calc_bem_once()
         # (the rotor loads are those of the reference pose, where _design_at_pose takes the turbine constants)
         bems = [] if rotor_device else None
-        sb = self._solve_statics_batch(cases, None, False, bems)
+        sb = self._solve_statics_batch(cases, None, False, bems, current_device=pose_device)
+        if pose_device:
+            parts = self._pose_device_chunks(fowt, cases, seas, sb, bems, tol, want, pose_chunk)
+            return self._pose_results(cases, sb, parts, host)
         X = sb["X"].cpu().numpy()
         C = sb["C_moor"].cpu().numpy()
         Fm = sb["F_moor"].cpu().numpy()
@@ -692,6 +769,12 @@ class Model:
             torch.cuda.synchronize(views[0].device)      # the chunk's tables are released below
             del res, views
         self._restore_reference_poses(X_ref)
+        return self._pose_results(cases, sb, parts, host)
+
+    def _pose_results(self, cases, sb, parts, host):
+        """The result of analyzeCasesBatch(statics=True) from the chunks' solves and the statics."""
+        import torch
+        n = len(cases)
         res = BatchResult({k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]} if parts else {})
         if n:
             res["Tmoor_PSD"], res["Tmoor_std"] = self._tension_channels(sb["J_moor"], res["Xi"])
@@ -841,7 +924,7 @@ class Model:
         return self.results
 
     def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
-                          pose_chunk=32, rotor_device=False, aero_device=False, channels=False):
+                          pose_chunk=32, rotor_device=False, aero_device=False, channels=False, pose_device=False):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -885,7 +968,18 @@ class Model:
         [n, nw, nrot], omega_ avg / std / max / min / PSD, torque_ and bPitch_ avg / std / PSD,
         power_avg and wind_PSD [n, nw], over every sea state of a case.  A batch with an operating
         rotor needs aero_device=True (the pair tensors live on the device only there); with
-        statics=True and on an array it raises NotImplementedError.  The default changes nothing."""
+        statics=True and on an array it raises NotImplementedError.  The default changes nothing.
+        pose_device=True (single FOWT, with statics=True) keeps the per-case design work of statics=True on
+        the device: the statics take the current loads of all cases from one rh_current_loads launch
+        (solveStaticsBatch's current_device), and every chunk of pose_chunk cases gets its node and member
+        tables at the cases' poses from one rh_pose_designs launch and its wave tables from one
+        rh_wave_tables_batch launch (raft/pose_device.py), so no FOWT is moved, no design uploaded and no
+        table launched per case.  Same result keys; the model stays at its reference pose.  Without
+        statics=True it raises ValueError; arrays, MacCamy-Fuchs members and designs with BEM excitation
+        raise NotImplementedError.  The default changes nothing."""
+        if pose_device and not statics:
+            raise ValueError("analyzeCasesBatch: pose_device=True needs statics=True (without it every case is solved "
+                             "at the reference pose and there is no per-case design)")
         if channels and statics:
             raise NotImplementedError("analyzeCasesBatch: channels=True with statics=True (the per-pose path keeps no "
                                       "pair tensors on the device; use saveTurbineOutputs per case there)")
@@ -899,7 +993,7 @@ class Model:
             raise NotImplementedError("analyzeCasesBatch: aero_device=True on an array (analyzeArrayBatch without "
                                       "statics does not evaluate rotors)")
         if statics:
-            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device)
+            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device, pose_device)
         if self.nFOWT != 1:
             return self.analyzeArrayBatch(cases, tol=tol, host=host, rotor_device=rotor_device)
         fowt = self.fowtList[0]
