@@ -12,8 +12,11 @@
 //     ring of kRingA1 / kRingC nodes (the two transverse rows of each).  The node loops run whole
 //     ring rounds with no load under a branch, so that every wait leaves the other slots' loads
 //     outstanding (tools/isa_check.py gates it).
-//   * Per-node bin sums: a 6-step DPP wave reduction (VALU only, no LDS or SGPR traffic),
-//     one partial per wave, summed in wave order.  Fixed order, so results are deterministic.
+//   * Per-node bin sums: transposing wave reductions of several sums at once (tbfly8 / tbfly4 /
+//     tbfly3: the rows first, two values per gfx950 row swap, then DPP inside the row; VALU only,
+//     no LDS or SGPR traffic), one partial per wave, summed in wave order.  Every sum meets the
+//     same partners in the same order whichever slot it is in, so results are deterministic and
+//     do not depend on how nodes are grouped.
 //   * The axial row of a node (projection 0) is read only where the node has axial side drag or
 //     end drag, in short loops of their own after the node loops of phases A and C; elsewhere it
 //     would meet coefficients that are exact zeros.
@@ -96,126 +99,83 @@ __device__ __forceinline__ double dpp_mov(double v) {   // full-mask permutation
   return __hiloint2double(hi, lo);
 }
 
-// t + t(lane ^ 32) and t + t(lane ^ 16) with the gfx950 row-swap instructions
-// (v_permlane32_swap / v_permlane16_swap: VALU, no LDS round trip as with ds_bpermute).
-// Called with both operands equal, the swap leaves {x_i, x_partner} split over its two
-// results in lane-dependent order, and their sum is the pair sum (bitwise the same as
-// t + __shfl_xor(t, 32 | 16): FP addition commutes).  Call with every lane active.
-__device__ __forceinline__ double xsum32(double t) {
-  const int lo = __double2loint(t), hi = __double2hiint(t);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+// Pair sums across the rows with the gfx950 row-swap instructions (v_permlane32_swap /
+// v_permlane16_swap: VALU, no LDS round trip as with ds_bpermute), two values per exchange.
+// v_permlane32_swap x, y exchanges the upper half of x with the lower half of y, so lane L of the
+// lower half is left with {x_L, x_(L^32)} and lane L of the upper half with {y_(L^32), y_L}: one add
+// gives the lower half x + x(lane ^ 32) and the upper half y + y(lane ^ 32), with no select and no
+// copy (FP addition commutes, so both lanes of a pair hold the same bits).  v_permlane16_swap does
+// the same with the odd rows of x and the even rows of y: even rows x + x(lane ^ 16), odd rows
+// y + y(lane ^ 16).  Call with every lane active.
+__device__ __forceinline__ double pair_sum32(double x, double y) {
+  const auto a = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(y), false, false);
+  const auto b = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(y), false, false);
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
-__device__ __forceinline__ double xsum16(double t) {
-  const int lo = __double2loint(t), hi = __double2hiint(t);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+__device__ __forceinline__ double pair_sum16(double x, double y) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(y), false, false);
+  const auto b = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(y), false, false);
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
 
-// Transposing butterfly: 16 per-lane values u[k] -> lane i of EVERY row ends with the wave
-// total (all 64 lanes) of value k(i) = 8 f0 + 4 f1 + 2 f2 + f3, with the lane bits
-//   f0 = b0^b2, f1 = b1^b2, f2 = b2^b3, f3 = b3     (i = lane & 15, b = bits of i).
-// Stage s pairs lane i with i^1 (quad_perm [1,0,3,2]), i^2 (quad_perm [2,3,0,1]), i^7
-// (row_half_mirror), i^15 (row_mirror); the f_s differ across each pair and agree on the
-// values both lanes still hold, so each lane keeps one half, sends the other, and the value
-// count halves per stage: 15 exchanges for 16 values instead of 16 full reductions.  The
-// four row sums are then combined across rows (lane^16, lane^32).  Fixed order everywhere.
-__device__ __forceinline__ double tbfly16(double (&u)[16], int lane) {
-  const int i = lane & 15;
-  const bool f0 = ((i ^ (i >> 2)) & 1) != 0, f1 = (((i >> 1) ^ (i >> 2)) & 1) != 0;
-  const bool f2 = (((i >> 2) ^ (i >> 3)) & 1) != 0, f3 = ((i >> 3) & 1) != 0;
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    const double keep = f0 ? u[p + 8] : u[p], send = f0 ? u[p] : u[p + 8];
-    u[p] = keep + dpp_mov<0xB1>(send);
-  }
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const double keep = f1 ? u[p + 4] : u[p], send = f1 ? u[p] : u[p + 4];
-    u[p] = keep + dpp_mov<0x4E>(send);
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const double keep = f2 ? u[p + 2] : u[p], send = f2 ? u[p] : u[p + 2];
-    u[p] = keep + dpp_mov<0x141>(send);
-  }
-  {
-    const double keep = f3 ? u[1] : u[0], send = f3 ? u[0] : u[1];
-    u[0] = keep + dpp_mov<0x140>(send);
-  }
-  return xsum32(xsum16(u[0]));
+// Transposing wave reductions: several per-lane values in, each lane out with the wave total (all 64
+// lanes) of one of them.  The cross-row exchanges come first, where the most values are, because a row
+// swap transposes a pair of values in 3 instructions (pair_sum32 / pair_sum16) where an in-row DPP
+// stage takes 7 (two selects, two moves, one add):
+//   tbfly8  ^32 on (u[p], u[p+4]), ^16 on (v[p], v[p+2]), one transposing DPP stage ^2, plain ^15, ^1, ^7
+//   tbfly4  ^32 on (a, c) and (b, d), ^16 on the two results, plain ^2, ^15, ^1, ^7: no select at all
+//   tbfly3  tbfly4 with the pad slot 0.0
+// (^1 quad_perm [1,0,3,2], ^2 quad_perm [2,3,0,1], ^7 row_half_mirror, ^15 row_mirror.)  Every value
+// meets its partners ^32, ^16, ^2, ^15, ^1, ^7 in that order whichever slot and whichever of the three it
+// is in, and every add is commutative, so a wave sum's bits do not depend on how the values are
+// grouped (tests/test_bfly_model.py is the order written out; the cross-mode tests rely on it).
+// The in-row order is one of many of equal cost and equal error bound; DESIGN.md §5 says why this one.
+//
+// tbfly4 / tbfly3: row r of the wave ends with value r (0 = a .. 3 = d or the pad), every lane of
+// the row with the same bits.  One writer per value: lanes 0, 16, 32, 48.
+__device__ __forceinline__ double tbfly4(double a, double b, double c, double d) {
+  double t = pair_sum16(pair_sum32(a, c), pair_sum32(b, d));
+  t += dpp_mov<0x4E>(t);
+  t += dpp_mov<0x140>(t);
+  t += dpp_mov<0xB1>(t);
+  t += dpp_mov<0x141>(t);
+  return t;
 }
-__device__ __forceinline__ int tbfly16_index(int lane) {
-  const int i = lane & 15;
-  return 8 * ((i ^ (i >> 2)) & 1) + 4 * (((i >> 1) ^ (i >> 2)) & 1) + 2 * (((i >> 2) ^ (i >> 3)) & 1) + ((i >> 3) & 1);
-}
+__device__ __forceinline__ double tbfly3(double a, double b, double c) { return tbfly4(a, b, c, 0.0); }
+// value a writer lane holds after tbfly4 (0 .. 3) / tbfly3 (0 .. 2), -1 for every other lane
+__device__ __forceinline__ int tbfly4_index(int lane) { return (lane & 15) == 0 ? lane >> 4 : -1; }
+__device__ __forceinline__ int tbfly3_index(int lane) { return (lane & 15) == 0 && lane < 48 ? lane >> 4 : -1; }
 
-// Three wave sums at once.  A 2-stage transposing butterfly inside each quad (partners i^1,
-// i^2: each lane keeps one of the values {a, b, c, 0}), then the quad sums are folded over
-// the row (row_ror 4, 8) and over the rows (lane^16, lane^32).  Every lane ends with the
-// wave total of value tbfly3_index(lane) (0 = a, 1 = b, 2 = c, 3 = pad): lanes 0, 2, 1
-// hold a, b, c.  33 instructions instead of 3 x 18 for three separate reductions.
-__device__ __forceinline__ double tbfly3(double a, double b, double c, int lane) {
-  const bool f0 = (lane & 1) != 0, f1 = (lane & 2) != 0;
-  // stage 0: pairs (a, c) and (b, 0): keep the second of each pair if f0
-  const double k0 = f0 ? c : a, s0 = f0 ? a : c;
-  const double k1 = f0 ? 0.0 : b, s1 = f0 ? b : 0.0;
-  const double u0 = k0 + dpp_mov<0xB1>(s0);
-  const double u1 = k1 + dpp_mov<0xB1>(s1);
-  // stage 1: pair (u0, u1): keep u1 if f1
-  double t = (f1 ? u1 : u0) + dpp_mov<0x4E>(f1 ? u0 : u1);
-  t += dpp_mov<0x124>(t);   // row_ror:4
-  t += dpp_mov<0x128>(t);   // row_ror:8
-  return xsum32(xsum16(t));
-}
-// value held by a lane after tbfly3: 2 f0 + f1 -> lane 0: a (0), lane 1: c (2), lane 2: b (1)
-__device__ __forceinline__ int tbfly3_index(int lane) { return 2 * (lane & 1) + ((lane >> 1) & 1); }
-
-// Four wave sums at once, no pad: the transverse sums (s_1, s_2) of two nodes, or the axial sums of
-// four.  Transposing stages with tbfly16's lane flags (partners i^1, i^2 within the 16-lane row):
-// (a, c), (b, d) -> two values, then one; the partners i^7 and i^15 hold the same value and are
-// added, then the rows (lane^16, lane^32).  7 exchanges.  Every value meets the partners ^1, ^2,
-// ^7, ^15, ^16, ^32 in that order whichever slot it is in (all commutative adds), so a wave sum's
-// bits do not depend on how the values are grouped.
-struct Bfly4 {   // a lane's stage flags and the value it holds after tbfly4 (formed once per phase A)
-  bool f0, f1, f2;
-  int vi;        // 0 = a .. 3 = d, or -1 (lanes >= 4 hold copies)
-  int vi8;       // (tbfly8) 0 .. 7, or -1 (lanes >= 8 hold copies)
+// tbfly8: eight wave sums at once (the transverse sums of a phase-A ring round's four nodes).  After the
+// two row stages a lane holds two values; the stage ^2 keeps one of them by the flag f0 = b1 ^ b2 (bits
+// of the lane), which differs across ^2 and agrees across ^15, ^1 and ^7, so that the three plain adds
+// meet lanes that hold the same value.  A lane ends with value 4 (lane >> 5) + 2 ((lane >> 4) & 1) + f0.
+// One writer per value: the lanes with (lane & 13) == 0 (0, 2, 16, 18, 32, 34, 48, 50), where f0 is
+// bit 1.  10 exchanges.
+struct Bfly4 {   // a lane's stage flag and the values it writes (formed once per phase A)
+  bool f0;
+  int vi;        // (tbfly4) 0 = a .. 3 = d, or -1 (not a writer lane)
+  int vi8;       // (tbfly8) 0 .. 7, or -1
 };
 __device__ __forceinline__ Bfly4 bfly4_lane(int lane) {
-  const int i = lane & 15;
   Bfly4 b;
-  b.f0 = ((i ^ (i >> 2)) & 1) != 0;
-  b.f1 = (((i >> 1) ^ (i >> 2)) & 1) != 0;
-  b.f2 = (((i >> 2) ^ (i >> 3)) & 1) != 0;
-  b.vi = lane >= 4 ? -1 : 2 * (lane & 1) + ((lane >> 1) & 1);
-  b.vi8 = lane >= 8 ? -1 : 4 * b.f0 + 2 * b.f1 + b.f2;
+  b.f0 = (((lane >> 1) ^ (lane >> 2)) & 1) != 0;
+  b.vi = tbfly4_index(lane);
+  b.vi8 = (lane & 13) != 0 ? -1 : 4 * (lane >> 5) + 2 * ((lane >> 4) & 1) + ((lane >> 1) & 1);
   return b;
 }
-// Eight wave sums at once (the transverse sums of a phase-A ring round's four nodes): three transposing
-// stages (partners i^1, i^2, i^7), 8 -> 4 -> 2 -> 1 values, then i^15 and the rows as tbfly4:
-// the same partners in the same order for every value, 10 exchanges.
 __device__ __forceinline__ double tbfly8(const double (&u)[8], const Bfly4& L) {
-  const bool f0 = L.f0, f1 = L.f1, f2 = L.f2;
+  const bool f0 = L.f0;
   double v[4], w[2];
 #pragma unroll
-  for (int p = 0; p < 4; ++p) v[p] = (f0 ? u[p + 4] : u[p]) + dpp_mov<0xB1>(f0 ? u[p] : u[p + 4]);
+  for (int p = 0; p < 4; ++p) v[p] = pair_sum32(u[p], u[p + 4]);
 #pragma unroll
-  for (int p = 0; p < 2; ++p) w[p] = (f1 ? v[p + 2] : v[p]) + dpp_mov<0x4E>(f1 ? v[p] : v[p + 2]);
-  double t = (f2 ? w[1] : w[0]) + dpp_mov<0x141>(f2 ? w[0] : w[1]);
+  for (int p = 0; p < 2; ++p) w[p] = pair_sum16(v[p], v[p + 2]);
+  double t = (f0 ? w[1] : w[0]) + dpp_mov<0x4E>(f0 ? w[0] : w[1]);
   t += dpp_mov<0x140>(t);
-  return xsum32(xsum16(t));
-}
-__device__ __forceinline__ double tbfly4(double a, double b, double c, double d, const Bfly4& L) {
-  const bool f0 = L.f0, f1 = L.f1;
-  const double v0 = (f0 ? c : a) + dpp_mov<0xB1>(f0 ? a : c);
-  const double v1 = (f0 ? d : b) + dpp_mov<0xB1>(f0 ? b : d);
-  double t = (f1 ? v1 : v0) + dpp_mov<0x4E>(f1 ? v0 : v1);
+  t += dpp_mov<0xB1>(t);
   t += dpp_mov<0x141>(t);
-  t += dpp_mov<0x140>(t);
-  return xsum32(xsum16(t));
+  return t;
 }
 
 template <int CTRL, int ROWS>
@@ -930,10 +890,10 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
               }
             }
           } else {
-            const int ln = lane_here();
-            const double tot = tbfly3(s1, s2, 0.0, ln);
-            if (ln < 3 && tbfly3_index(ln) < 2 && nr < nn) {
-              double& rr = red[(nr * 3 + 1 + tbfly3_index(ln)) * LW + wv_s];
+            const double tot = tbfly3(s1, s2, 0.0);
+            const int vi = tbfly3_index(lane_here());
+            if (vi >= 0 && vi < 2 && nr < nn) {   // lanes 0, 16
+              double& rr = red[(nr * 3 + 1 + vi) * LW + wv_s];
               rr = (GX && p > 0) ? rr + tot : tot;   // passes add in pass order
             }
           }
@@ -964,12 +924,11 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
         int vi;
         double tot;
         if constexpr (kQuad) {
-          tot = tbfly4(q[0], q[1], q[2], q[3], bl);
+          tot = tbfly4(q[0], q[1], q[2], q[3]);
           vi = bl.vi;
         } else {
-          const int ln = lane_here();
-          tot = tbfly3(q[0], q[1], q[2], ln);
-          vi = ln < 3 ? tbfly3_index(ln) : -1;
+          tot = tbfly3(q[0], q[1], q[2]);
+          vi = tbfly3_index(lane_here());
         }
         if (vi >= 0 && k0 + vi < nn) {
           const int n = ax[12 * (k0 + vi) + 11];
@@ -1329,10 +1288,9 @@ __global__ __launch_bounds__(LT, LT >= 256 ? 512 / LT : 2) void k_solve_lds(Case
             }
           }
           if (a.o.std) {   // the bin's six sums over the wave by two transposing butterflies
-            const int ln = lane_here();
-            const double t0 = tbfly3(m2v[0], m2v[1], m2v[2], ln), t1 = tbfly3(m2v[3], m2v[4], m2v[5], ln);
-            if (ln < 3) {
-              const int k = tbfly3_index(ln);
+            const double t0 = tbfly3(m2v[0], m2v[1], m2v[2]), t1 = tbfly3(m2v[3], m2v[4], m2v[5]);
+            const int k = tbfly3_index(lane_here());
+            if (k >= 0) {   // lanes 0, 16, 32
               sred[wv * 6 + k] += t0;
               sred[wv * 6 + 3 + k] += t1;
             }

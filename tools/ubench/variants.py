@@ -36,7 +36,7 @@ EDITS = {
     "aNoComp": [("rh_solve.hip", "        s1 = s2 = 0;\n#pragma unroll\n        for (int j = 0; j < NB; ++j) {\n          const double z = bz[j];",
                       "        s1 = s2 = 0;\n#pragma unroll\n        for (int j = 0; j < NB; ++j) { s1 += K[0][j].r + K[0][j].i; s2 += K[1][j].r + K[1][j].i; }\n        return;\n"
                       "#pragma unroll\n        for (int j = 0; j < NB; ++j) {\n          const double z = bz[j];")],
-    "aNoBfly": [("rh_solve.hip", "            const double tot = tbfly3(s1, s2, 0.0, ln);", "            const double tot = s1 + s2;")],
+    "aNoBfly": [("rh_solve.hip", "            const double tot = tbfly3(s1, s2, 0.0);", "            const double tot = s1 + s2;")],
     # k_qtf_gemm: no pair scalars of the potential, no bilinear / no potential-channel k-steps, no stores,
     # the upper triangle only
     "gNoPot": [("rh_qtf_mfma.hip", "      qtf_pot_scalars(q.w2[i1], q.k2[i1], tkh[x >> 4], q.w2[i2], q.k2[i2], tkh[16 + (x & 15)], cb, sb, h, g, sp, sm);",
