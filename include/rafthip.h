@@ -253,7 +253,8 @@ int rh_bem_excitation_batch(rh_ctx* ctx, int ndesign, const rh_bem_design* desig
 
 /* ---- quasi-static mooring and mean offsets (csrc/rh_moor.h, rh_moor.hip) ----
  * The device form of raft/mooring.py for ONE coupled body whose lines each join one fixed point
- * and one body-attached point (no free points, no current on the lines, W >= 0), and of
+ * and one body-attached point (no free points, W >= 0; a uniform current on the lines through
+ * rh_moor_eval_current / rh_statics_solve_current), and of
  * Model.solveStatics' Newton on it.  One lane per (pose, line); the lines of a pose sit in
  * adjacent lanes of a group of the next power of two >= the largest nline, at most 64.
  * Several bodies, free points and shared lines: rh_moor_array_eval / rh_array_statics_solve below. */
@@ -300,6 +301,28 @@ int rh_moor_eval(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* s
 int rh_statics_solve(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int ncase,
                      const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
                      const double* warm0, double* X, double* warm, int* iters, int* status, rh_stream stream);
+
+/* The two calls above with a uniform current on the lines (MooringSystem.current, mooring
+ * currentMod 1): Line.static_solve(current=U) of every line, the drag evaluated on the chord at
+ * each evaluated pose (the central differences of J included).  drag: device
+ * [nsys][RH_MD_COUNT][nl_max], the drag of each line's type; columns of lines a system does not
+ * have are zeros; the RH_MD_RHO row holds the system's MooringSystem.rho.  current: device
+ * [npose][3] / [ncase][3] [m/s], global; all three components are honoured.  A pose whose current
+ * is exactly (0, 0, 0) gets the bits of the call without current.  Everything else as above. */
+enum rh_moor_drag_field {
+  RH_MD_D,    /* line diameter [m] */
+  RH_MD_CD,   /* transverse drag coefficient */
+  RH_MD_CDAX, /* tangential drag coefficient */
+  RH_MD_RHO,  /* water density [kg/m^3] */
+  RH_MD_COUNT
+};
+int rh_moor_eval_current(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int npose,
+                         const int* sys_idx, const double* r6, const double* drag, const double* current,
+                         double* warm, double* F, double* K, double* T, double* J, int* status, rh_stream stream);
+int rh_statics_solve_current(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int ncase,
+                             const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
+                             const double* drag, const double* current, const double* warm0, double* X, double* warm,
+                             int* iters, int* status, rh_stream stream);
 
 /* ---- general mooring systems and the mean offsets of moored arrays (csrc/rh_moor_array.h, .hip) ----
  * The device form of raft/mooring.py for several coupled bodies (one per FOWT), free points solved

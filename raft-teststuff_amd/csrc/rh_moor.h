@@ -1,13 +1,16 @@
 // rh_moor.h -- quasi-static mooring and the mean-offset Newton, written once for host and device.
 //
 // FP64 restatement, operation for operation, of raft/mooring.py (catenary, Line.static_solve
-// without current, Body.set_position, body_forces, coupled_stiffness_analytic, tensions,
-// coupled_stiffness_fd's tension Jacobian) and of Model.solveStatics' eval_func / step_func with
-// raft/dsolve.py's dsolve2.  The same code is compiled for gfx950 (rh_moor.hip) and for the CPU
-// check against the Python (tests/test_moor_host.py builds tools/moor_host.cpp with g++).
+// without and with a uniform current, Line.current_load, Body.set_position, body_forces,
+// coupled_stiffness_analytic, tensions, coupled_stiffness_fd's tension Jacobian) and of
+// Model.solveStatics' eval_func / step_func with raft/dsolve.py's dsolve2.  The same code is
+// compiled for gfx950 (rh_moor.hip) and for the CPU check against the Python (tests/test_moor_host.py
+// builds tools/moor_host.cpp with g++, tests/test_moor_current_host.py tools/moor_current_host.cpp).
 //
-// Scope: ONE coupled body whose lines each join one fixed point and one body-attached point, no
-// current on the lines, W >= 0.  Everything else is refused in raft/mooring_device.py.
+// Scope: ONE coupled body whose lines each join one fixed point and one body-attached point,
+// W >= 0, with or without a uniform current on the lines (numpy's norm and matrix products may
+// differ from the plain C order below in the last bits).  Everything else is refused in
+// raft/mooring_device.py.
 //
 // Lock step: on the device the lines of a case sit in adjacent lanes and the per-case sums go
 // through shuffles, so every lane of a wave has to reach them.  Loops therefore run until the
@@ -230,6 +233,12 @@ RH_HD inline void body_point(const double* r6, double ax, double ay, double az, 
   rz = R20 * ax + R21 * ay + R22 * az;
 }
 
+// What Line.current_load reads besides the chord: the line type's drag and the case's current.
+struct LineCur {
+  double d, Cd, CdAx, rho;      // diameter [m], transverse and tangential drag coefficients, water density
+  double Ux, Uy, Uz;            // uniform current [m/s], global
+};
+
 RH_HD inline void line_solve(const LineIn& ln, bool run, const double* r6, double depth, double tol, double HF0,
                              double VF0, LineSol& s) {
   RH_MOOR_NOFMA
@@ -260,6 +269,124 @@ RH_HD inline void line_solve(const LineIn& ln, bool run, const double* r6, doubl
   s.Ku[6] = c * k.K10;
   s.Ku[7] = sn * k.K10;
   s.Ku[8] = k.K11;
+  const double fAx = swap ? fux : flx, fAy = swap ? fuy : fly, fAz = swap ? fuz : flz;
+  const double fBx = swap ? flx : fux, fBy = swap ? fly : fuy, fBz = swap ? flz : fuz;
+  s.TA = sqrt(fAx * fAx + fAy * fAy + fAz * fAz);
+  s.TB = sqrt(fBx * fBx + fBy * fBy + fBz * fBz);
+  s.fx = attA ? fAx : fBx;
+  s.fy = attA ? fAy : fBy;
+  s.fz = attA ? fAz : fBz;
+  s.rx = px - r6[0];
+  s.ry = py - r6[1];
+  s.rz = pz - r6[2];
+  s.HF = k.HF;
+  s.VF = k.VF;
+  s.iters = k.iters;
+  s.status = k.status;
+  const bool ok = run && (k.status == kOk || k.status == kCatNotConverged);
+  if (!ok) {   // padding lanes and refused lines contribute zeros
+    s.fx = s.fy = s.fz = 0.0;
+    s.TA = s.TB = 0.0;
+    RH_MOOR_UNROLL
+    for (int i = 0; i < 9; ++i) s.Ku[i] = 0.0;
+    s.HF = s.VF = 0.0;
+  }
+}
+
+// Line.static_solve(current=U) at body pose r6: line_solve with the current branch.  The wet
+// weight plus Line.current_load on the chord at THIS pose is the distributed load (so the central
+// differences of the tension Jacobian re-evaluate the drag on each perturbed chord, as
+// coupled_stiffness_fd does by calling static_solve again); the catenary is solved with
+// W' = |load| in the frame R whose -z axis is the load's direction, and forces and stiffness are
+// rotated back.  A lane whose current is exactly (0, 0, 0) takes line_solve's values through
+// selects, bit for bit (np.any(current) is false in the Python); the current / no-current and
+// the up / no-up choices are selects, never early exits, so every lane reaches the catenary's
+// votes.  (A function of its own, not a variant of line_solve: the kernels without current keep
+// their instructions.)
+// branch: bit 0 = the current branch was taken, bit 1 = the load points up (R0 applied, CB = -1).
+RH_HD inline void line_solve_current(const LineIn& ln, const LineCur& cu, bool run, const double* r6, double depth,
+                                     double tol, double HF0, double VF0, LineSol& s, int& branch) {
+  RH_MOOR_NOFMA
+  double qx, qy, qz;
+  body_point(r6, ln.ax, ln.ay, ln.az, qx, qy, qz);
+  const double px = r6[0] + qx, py = r6[1] + qy, pz = r6[2] + qz;   // the attached point, global
+  const bool attA = ln.att_end == 0;
+  const double Ax = attA ? px : ln.fx, Ay = attA ? py : ln.fy, Az = attA ? pz : ln.fz;
+  const double Bx = attA ? ln.fx : px, By = attA ? ln.fy : py, Bz = attA ? ln.fz : pz;
+  const bool cur = cu.Ux != 0.0 || cu.Uy != 0.0 || cu.Uz != 0.0;
+  // current_load: transverse and tangential drag per unit length on the chord A -> B
+  const double ex = Bx - Ax, ey = By - Ay, ez = Bz - Az;
+  const double en = sqrt(ex * ex + ey * ey + ez * ez);
+  const double tx = en > 0.0 ? ex / en : 0.0, ty = en > 0.0 ? ey / en : 0.0, tz = en > 0.0 ? ez / en : 1.0;
+  const double ut = cu.Ux * tx + cu.Uy * ty + cu.Uz * tz;
+  const double Utx = ut * tx, Uty = ut * ty, Utz = ut * tz;
+  const double Unx = cu.Ux - Utx, Uny = cu.Uy - Uty, Unz = cu.Uz - Utz;
+  const double kn = 0.5 * cu.rho * cu.d * cu.Cd * sqrt(Unx * Unx + Uny * Uny + Unz * Unz);
+  const double kt = 0.5 * cu.rho * 3.141592653589793 * cu.d * cu.CdAx * sqrt(Utx * Utx + Uty * Uty + Utz * Utz);
+  // the distributed load (0, 0, -W) + drag, its size W' and its direction a
+  const double f0 = 0.0 + (kn * Unx + kt * Utx);
+  const double f1 = 0.0 + (kn * Uny + kt * Uty);
+  const double f2 = -ln.W + (kn * Unz + kt * Utz);
+  const double Wc = sqrt(f0 * f0 + f1 * f1 + f2 * f2);
+  const double W = cur ? Wc : ln.W;
+  const double a0 = f0 / Wc, a1r = f1 / Wc, a2r = f2 / Wc;
+  const bool up = cur && a2r > 0.0;   // the net load points away from the seabed
+  // a load with an upward component is first turned 180 deg about x (R0 = diag(1, -1, -1)), so
+  // that the Rodrigues step is taken at 1 + cos >= 1
+  const double a1 = up ? -a1r : a1r, a2 = up ? -a2r : a2r;
+  const double v0 = a1 * -1.0 - a2 * 0.0, v1 = a2 * 0.0 - a0 * -1.0;   // a x (0, 0, -1)
+  const double den = 1.0 + (-a2);
+  // R = (I + V + V V / (1 + cos)) R0, V the cross-product matrix of v = (v0, v1, 0): R a = (0, 0, -1)
+  const double r01 = (v1 * v0) / den, r10 = (v0 * v1) / den;
+  const double r11 = 1.0 + (-(v0 * v0)) / den, r22 = 1.0 + (-(v1 * v1) - v0 * v0) / den;
+  const double R[9] = {1.0 + (-(v1 * v1)) / den, up ? -r01 : r01, up ? -v1 : v1,
+                       r10, up ? -r11 : r11, up ? v0 : -v0,
+                       -v1, up ? -v0 : v0, up ? -r22 : r22};
+  // the ends are ordered by height along the load
+  const double zA = cur ? R[6] * Ax + R[7] * Ay + R[8] * Az : Az;
+  const double zB = cur ? R[6] * Bx + R[7] * By + R[8] * Bz : Bz;
+  const bool swap = zB < zA;   // the catenary runs from the lower end to the upper one
+  const double lx = swap ? Bx : Ax, ly = swap ? By : Ay, lz = swap ? Bz : Az;
+  const double ux = swap ? Ax : Bx, uy = swap ? Ay : By, uz = swap ? Az : Bz;
+  const double gx = ux - lx, gy = uy - ly, gz = uz - lz;
+  const double dx = cur ? R[0] * gx + R[1] * gy + R[2] * gz : gx;
+  const double dy = cur ? R[3] * gx + R[4] * gy + R[5] * gz : gy;
+  const double dz = cur ? R[6] * gx + R[7] * gy + R[8] * gz : gz;
+  const double LH = hypot(dx, dy);
+  const double c = LH > 0.0 ? dx / LH : 0.0;
+  const double sn = LH > 0.0 ? dy / LH : 0.0;
+  // off the seabed: no contact (the global depth of the end that ordering calls lower); pulled
+  // away from the seabed: never in contact
+  const double CB = up ? -1.0 : lz > -depth ? -depth - lz : 0.0;
+  const CatOut k = catenary(LH, dz, ln.L, ln.EA, W, CB, tol, HF0, VF0, run);
+  const double hux = -k.HF * c, huy = -k.HF * sn, huz = -k.VF;
+  const double hlx = k.HA * c, hly = k.HA * sn, hlz = k.VA;
+  const double Kt = LH > 0.0 ? k.HF / LH : 0.0;   // transverse (geometric) stiffness
+  const double Kl[9] = {c * c * k.K00 + sn * sn * Kt, c * sn * (k.K00 - Kt), c * k.K01,
+                        c * sn * (k.K00 - Kt), sn * sn * k.K00 + c * c * Kt, sn * k.K01,
+                        c * k.K10, sn * k.K10, k.K11};
+  // back to the global frame: R' f and R' Ku R
+  const double fux = cur ? R[0] * hux + R[3] * huy + R[6] * huz : hux;
+  const double fuy = cur ? R[1] * hux + R[4] * huy + R[7] * huz : huy;
+  const double fuz = cur ? R[2] * hux + R[5] * huy + R[8] * huz : huz;
+  const double flx = cur ? R[0] * hlx + R[3] * hly + R[6] * hlz : hlx;
+  const double fly = cur ? R[1] * hlx + R[4] * hly + R[7] * hlz : hly;
+  const double flz = cur ? R[2] * hlx + R[5] * hly + R[8] * hlz : hlz;
+  double M[9];   // R' Ku
+  RH_MOOR_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    RH_MOOR_UNROLL
+    for (int j = 0; j < 3; ++j) M[3 * i + j] = R[i] * Kl[j] + R[3 + i] * Kl[3 + j] + R[6 + i] * Kl[6 + j];
+  }
+  RH_MOOR_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    RH_MOOR_UNROLL
+    for (int j = 0; j < 3; ++j) {
+      const double g = M[3 * i] * R[j] + M[3 * i + 1] * R[3 + j] + M[3 * i + 2] * R[6 + j];
+      s.Ku[3 * i + j] = cur ? g : Kl[3 * i + j];
+    }
+  }
+  branch = (cur ? 1 : 0) | (up ? 2 : 0);
   const double fAx = swap ? fux : flx, fAy = swap ? fuy : fly, fAz = swap ? fuz : flz;
   const double fBx = swap ? flx : fux, fBy = swap ? fly : fuy, fBz = swap ? flz : fuz;
   s.TA = sqrt(fAx * fAx + fAy * fAy + fAz * fAz);

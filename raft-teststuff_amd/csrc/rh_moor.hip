@@ -1,5 +1,6 @@
 // rh_moor.hip -- quasi-static mooring and mean offsets on the device: the kernels over the
-// host/device math of rh_moor.h, and their two ABI calls (rh_moor_eval, rh_statics_solve).
+// host/device math of rh_moor.h, and their ABI calls (rh_moor_eval, rh_statics_solve, and the two
+// with a uniform current on the lines, rh_moor_eval_current and rh_statics_solve_current).
 // Included by rh_abi.hip after its `fail` / RH_HIP helpers.
 //
 // Mapping: one lane per (pose, line).  The lines of a pose sit in adjacent lanes of a group of
@@ -11,6 +12,13 @@
 // to the wave's vote with finished lanes predicated off (rh_moor.h), so all 64 lanes reach every
 // shuffle and a pose's numbers never depend on the poses next to it.  No LDS; FP64 VALU only;
 // plain vector loads and stores.
+//
+// Current on the lines: k_moor_eval_current and k_statics_solve_current (rh_moor_current.hip, a
+// translation unit of its own that includes this file with RH_MOOR_CURRENT_UNIT defined for the
+// lane helpers) are siblings of the two kernels here.  They are siblings and not instantiations of
+// shared templates, and live in another unit, because the kernels without current have to keep
+// their instructions (tools/asm_same.py): a shared templated body, or the mere presence of further
+// callers of rh_moor.h's inline functions in the unit, gives them another register allocation.
 #pragma once
 #include "rh_common.h"
 #include "rh_moor.h"
@@ -93,6 +101,7 @@ __device__ __forceinline__ bool moor_lane_setup(const rh_moor_system* __restrict
   return sys_ok;
 }
 
+#ifndef RH_MOOR_CURRENT_UNIT
 // grid ceil(npose gw / 256), 256 threads
 __global__ __launch_bounds__(256) void k_moor_eval(const rh_moor_system* __restrict__ sys, int nsys, int npose, int gw,
                                                    int nl_max, const int* __restrict__ sys_idx,
@@ -195,8 +204,20 @@ __global__ __launch_bounds__(256) void k_statics_solve(const rh_moor_system* __r
   }
 }
 
+// (defined in rh_moor_current.hip)
+hipError_t launch_moor_eval_current(dim3 grid, hipStream_t s, const rh_moor_system* sys, int nsys, int npose, int gw,
+                                    int nl_max, const int* sys_idx, const double* r6, const double* drag,
+                                    const double* current, double* warm, double* F, double* K, double* T, double* J,
+                                    int* status);
+hipError_t launch_statics_solve_current(dim3 grid, hipStream_t s, const rh_moor_system* sys, int nsys, int ncase, int gw,
+                                        int nl_max, const int* sys_idx, const double* X_ref, const double* K_hs,
+                                        const double* F_const, const double* drag, const double* current,
+                                        const double* warm0, double* X, double* warm, int* iters, int* status);
+#endif   // RH_MOOR_CURRENT_UNIT
+
 }  // namespace rh
 
+#ifndef RH_MOOR_CURRENT_UNIT
 namespace {
 // validates the host records; returns the group width through gw and the largest nline through nl_max
 int check_moor_systems(const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int n, const char* who,
@@ -252,3 +273,39 @@ int rh_statics_solve(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_syste
   RH_HIP(hipGetLastError());
   return RH_OK;
 }
+
+int rh_moor_eval_current(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int npose,
+                         const int* sys_idx, const double* r6, const double* drag, const double* current,
+                         double* warm, double* F, double* K, double* T, double* J, int* status, rh_stream stream) {
+  if (!ctx) return fail(RH_EINVAL, "rh_moor_eval_current: null context");
+  int gw, nl_max;
+  if (int r = check_moor_systems(sys, sys_dev, nsys, npose, "rh_moor_eval_current", gw, nl_max)) return r;
+  if (!drag || !current) return fail(RH_EINVAL, "rh_moor_eval_current: null drag or current");
+  if (npose == 0) return RH_OK;
+  if (!r6 || !F || !K || !T || !status) return fail(RH_EINVAL, "rh_moor_eval_current: null r6, F, K, T or status");
+  RH_HIP(hipSetDevice(ctx->device));
+  const long long lanes = (long long)npose * gw;
+  RH_HIP(rh::launch_moor_eval_current(dim3((unsigned)((lanes + 255) / 256)), (hipStream_t)stream, sys_dev, nsys, npose, gw,
+                                      nl_max, sys_idx, r6, drag, current, warm, F, K, T, J, status));
+  return RH_OK;
+}
+
+int rh_statics_solve_current(rh_ctx* ctx, const rh_moor_system* sys, const rh_moor_system* sys_dev, int nsys, int ncase,
+                             const int* sys_idx, const double* X_ref, const double* K_hs, const double* F_const,
+                             const double* drag, const double* current, const double* warm0, double* X, double* warm,
+                             int* iters, int* status, rh_stream stream) {
+  if (!ctx) return fail(RH_EINVAL, "rh_statics_solve_current: null context");
+  int gw, nl_max;
+  if (int r = check_moor_systems(sys, sys_dev, nsys, ncase, "rh_statics_solve_current", gw, nl_max)) return r;
+  if (!drag || !current) return fail(RH_EINVAL, "rh_statics_solve_current: null drag or current");
+  if (ncase == 0) return RH_OK;
+  if (!X_ref || !K_hs || !F_const || !X || !warm || !iters || !status)
+    return fail(RH_EINVAL, "rh_statics_solve_current: null X_ref, K_hs, F_const, X, warm, iters or status");
+  RH_HIP(hipSetDevice(ctx->device));
+  const long long lanes = (long long)ncase * gw;
+  RH_HIP(rh::launch_statics_solve_current(dim3((unsigned)((lanes + 255) / 256)), (hipStream_t)stream, sys_dev, nsys,
+                                          ncase, gw, nl_max, sys_idx, X_ref, K_hs, F_const, drag, current, warm0, X, warm,
+                                          iters, status));
+  return RH_OK;
+}
+#endif   // RH_MOOR_CURRENT_UNIT

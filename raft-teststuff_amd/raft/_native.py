@@ -73,6 +73,9 @@ class RhMoorSystem(ctypes.Structure):
 # line-table field order (enum rh_moor_line_field)
 MOOR_LINE_FIELDS = ["FX", "FY", "FZ", "AX", "AY", "AZ", "L", "EA", "W", "END"]
 ML_COUNT = len(MOOR_LINE_FIELDS)
+# drag-table row order of the calls with current on the lines (enum rh_moor_drag_field)
+MOOR_DRAG_FIELDS = ["D", "CD", "CDAX", "RHO"]
+MD_COUNT = len(MOOR_DRAG_FIELDS)
 MOOR_MAX_LINES = 64
 MOOR_STATUS = {0: "ok", 1: "catenary: XF < 0", 2: "catenary: L <= 0", 3: "catenary: EA <= 0",
                4: "catenary did not converge", 5: "statics Newton did not converge", 6: "singular step matrix",
@@ -178,6 +181,10 @@ def lib():
                                  _p, _p, _p],
                 "rh_statics_solve": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,
                                      _p, _p, _p, _p, _p, _p],
+                "rh_moor_eval_current": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p, _p,
+                                         _p, _p, _p, _p, _p, _p, _p],
+                "rh_statics_solve_current": [_p, ctypes.POINTER(RhMoorSystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p,
+                                             _p, _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_moor_array_eval": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p, _p, _p,
                                        _p, _p, _p, _p, _p, _p, _p, _p],
                 "rh_array_statics_solve": [_p, ctypes.POINTER(RhMoorArraySystem), _p, ctypes.c_int, ctypes.c_int, _p,

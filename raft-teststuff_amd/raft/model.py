@@ -433,23 +433,47 @@ class Model:
                 F_const[ic, i] = F_und[i] + F_env
         return F_const
 
-    def _statics_batch_inputs(self, cases, F_extra=None, bems=None, current_device=False):
+    def _line_currents(self, cases):
+        """The uniform current on the mooring lines of every case, [n, 3], by solveStatics' rule:
+        speed (cos heading, sin heading, 0) with mooring currentMod > 0 and a positive speed, else zero."""
+        cur = np.zeros([len(cases), 3])
+        if self.mooring_currentMod > 0:
+            for i, case in enumerate(cases):
+                speed = get_from_dict(case, "current_speed", shape=0, default=0.0)
+                head = get_from_dict(case, "current_heading", shape=0, default=0)
+                if speed > 0:
+                    cur[i] = [speed * np.cos(np.radians(head)), speed * np.sin(np.radians(head)), 0.0]
+        return cur
+
+    def _refuse_array_line_current(self, who):
+        if self.nFOWT != 1 or self.ms is not None:
+            raise NotImplementedError(f"{who}: line_current=True on an array (current on array-level, shared and "
+                                      "free-point lines is not on the device: the host model it would restate does "
+                                      "not solve the moored-array design in current; DESIGN.md §7)")
+
+    def _statics_batch_inputs(self, cases, F_extra=None, bems=None, current_device=False, line_current=False):
         """The host side of solveStaticsBatch: the device mooring system, X_ref [6], K_hs [6,6],
         F_const [n,6] = W_struc + W_hydro + F_env (+ F_extra) and the line warm state at X_ref.
+        line_current: the cases' currents go to the device per case, so a currentMod 1 design is not refused.
         bems: None (the host evaluates the rotors), or a list, filled here after every refusal with the
         rotors' device loads at X_ref (_array_rotor_loads) for the caller that needs them again.
         current_device: the current loads of all cases from one launch (FOWT.currentLoadsBatch at X_ref)."""
         from .mooring_device import DeviceMooring, warm_state
+        if line_current:
+            self._refuse_array_line_current("solveStaticsBatch")
         if self.nFOWT != 1 or self.ms is not None:
             raise NotImplementedError("solveStaticsBatch: a single FOWT with its own mooring system (arrays and "
                                       "array-level mooring are solved by solveStatics)")
         fowt = self.fowtList[0]
         if fowt.ms is None:
             raise NotImplementedError("solveStaticsBatch: the FOWT has no mooring system")
-        if self.mooring_currentMod > 0 and any(get_from_dict(c, "current_speed", shape=0, default=0.0) > 0
-                                               for c in cases):
-            raise NotImplementedError("solveStaticsBatch: current on the mooring lines (mooring currentMod 1)")
-        fowt.ms.current = np.zeros(3)                    # as solveStatics clears it for a case without one
+        if not line_current and self.mooring_currentMod > 0 and any(
+                get_from_dict(c, "current_speed", shape=0, default=0.0) > 0 for c in cases):
+            raise NotImplementedError("solveStaticsBatch: current on the mooring lines (mooring currentMod 1); pass "
+                                      "line_current=True to solve it on the device")
+        # the host object carries no current: the device takes it per case (with line_current), and
+        # solveStatics clears it for a case without one
+        fowt.ms.current = np.zeros(3)
         if getattr(self, "_moor_dev", None) is None or self._moor_dev[0] is not fowt.ms:
             self._moor_dev = (fowt.ms, DeviceMooring([fowt.ms], self.device))
         dm = self._moor_dev[1]
@@ -466,7 +490,8 @@ class Model:
             F_const += np.asarray(F_extra, dtype=float).reshape(len(cases), 6)
         return dm, X_ref, K_hs, F_const, warm0
 
-    def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False, current_device=False):
+    def solveStaticsBatch(self, cases, F_extra=None, host=True, rotor_device=False, current_device=False,
+                          line_current=False):
         """The mean offsets of many load cases in two device launches (rh_statics_solve, then
         rh_moor_eval at the solved poses): solveStatics' Newton per case, every case's lines in
         adjacent lanes (csrc/rh_moor.hip).  A single FOWT with its own mooring system; F_extra
@@ -479,15 +504,25 @@ class Model:
         one host CCBlade evaluation per case; a case whose rotor solve fails raises RuntimeError.
         current_device=True takes the current loads of all cases from one rh_current_loads launch
         (FOWT.currentLoadsBatch) instead of one calcCurrentLoads per case; the rest of the environmental
-        loads is unchanged.  The defaults change nothing."""
-        return self._solve_statics_batch(cases, F_extra, host, [] if rotor_device else None, current_device)
+        loads is unchanged.
+        line_current=True solves a mooring currentMod 1 design: each case's uniform current on the lines
+        (solveStatics' rule: speed (cos heading, sin heading, 0) with a positive current_speed, else
+        zero) goes into the Newton (rh_statics_solve_current) and into the evaluation at the solved poses
+        (rh_moor_eval_current), so F_moor, C_moor, Tmoor_avg and J_moor are those of the host system
+        with that case's current still set, as analyzeCases reads them after solveStatics.  Without it
+        such a design with a current case raises NotImplementedError; on an array it raises too.
+        The defaults change nothing."""
+        return self._solve_statics_batch(cases, F_extra, host, [] if rotor_device else None, current_device,
+                                         line_current)
 
-    def _solve_statics_batch(self, cases, F_extra, host, bems, current_device=False):
+    def _solve_statics_batch(self, cases, F_extra, host, bems, current_device=False, line_current=False):
         """solveStaticsBatch with the rotor loads as _statics_batch_inputs takes them."""
-        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, bems, current_device)
+        dm, X_ref, K_hs, F_const, warm0 = self._statics_batch_inputs(cases, F_extra, bems, current_device, line_current)
+        cur = self._line_currents(cases) if line_current else None
         n = len(cases)
-        sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)))
-        ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True)
+        sol = dm.solve_statics(np.tile(X_ref, (n, 1)), np.tile(K_hs, (n, 1, 1)), F_const, np.tile(warm0, (n, 1, 1)),
+                               current=cur)
+        ev = dm.eval(sol["X"], warm=sol["warm"], jacobian=True, current=cur)
         torch = dm.torch
         status = torch.maximum(sol["status"], ev["status"])
         out = dict(X=sol["X"], Xi0=sol["X"] - torch.tensor(X_ref, dtype=torch.float64, device=dm.device),
@@ -723,15 +758,19 @@ class Model:
         fowt._dd = fowt._host = None
         return parts
 
-    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False, pose_device=False):
+    def _analyze_cases_statics(self, cases, tol, want, host, pose_chunk, rotor_device=False, pose_device=False,
+                               line_current=False):
         """analyzeCasesBatch(statics=True): every case at its own mean-offset pose, as
         analyzeCases solves it when the mooring is a system.  Offsets, C_moor and the tension
         Jacobian of every case come from solveStaticsBatch; each case then gets its own
         DeviceDesign (the FOWT moved to its pose exactly as solveStatics leaves it: turbine and
         hydro constants at the reference pose, members and rotors at the offset pose, C_moor from
         the device), and the drag fixed points run in chunks of pose_chunk views.  pose_device: the
-        current loads of the statics and every chunk's designs from the device (_pose_device_chunks)."""
+        current loads of the statics and every chunk's designs from the device (_pose_device_chunks).
+        line_current: the statics with each case's current on the mooring lines (solveStaticsBatch's)."""
         import torch
+        if line_current:
+            self._refuse_array_line_current("analyzeCasesBatch(statics=True)")
         if self.nFOWT != 1 or self.ms is not None:
             raise NotImplementedError("analyzeCasesBatch(statics=True): arrays (their statics couple the FOWTs; "
                                       "use analyzeCases)")
@@ -748,7 +787,8 @@ class Model:
         self._calc_bem_once()
         # (the rotor loads are those of the reference pose, where _design_at_pose takes the turbine constants)
         bems = [] if rotor_device else None
-        sb = self._solve_statics_batch(cases, None, False, bems, current_device=pose_device)
+        sb = self._solve_statics_batch(cases, None, False, bems, current_device=pose_device,
+                                       line_current=line_current)
         if pose_device:
             parts = self._pose_device_chunks(fowt, cases, seas, sb, bems, tol, want, pose_chunk)
             return self._pose_results(cases, sb, parts, host)
@@ -924,7 +964,8 @@ class Model:
         return self.results
 
     def analyzeCasesBatch(self, cases, tol=0.01, want=("psd", "std", "zeta", "B_drag"), host=True, statics=False,
-                          pose_chunk=32, rotor_device=False, aero_device=False, channels=False, pose_device=False):
+                          pose_chunk=32, rotor_device=False, aero_device=False, channels=False, pose_device=False,
+                          line_current=False):
         """Solve many cases in one device call (one workgroup per case's drag fixed point).
         cases: list of case dicts (wave_heading/spectrum/period/height/gamma, each a scalar or
         one entry per sea state; with wind_speed > 0 on an operating rotor, that case's
@@ -976,7 +1017,16 @@ class Model:
         rh_wave_tables_batch launch (raft/pose_device.py), so no FOWT is moved, no design uploaded and no
         table launched per case.  Same result keys; the model stays at its reference pose.  Without
         statics=True it raises ValueError; arrays, MacCamy-Fuchs members and designs with BEM excitation
-        raise NotImplementedError.  The default changes nothing."""
+        raise NotImplementedError.  The default changes nothing.
+        line_current=True (single FOWT, with statics=True) solves a mooring currentMod 1 design with each
+        case's uniform current on the mooring lines (solveStaticsBatch's line_current): offsets, C_moor,
+        F_moor0, Tmoor_avg and the tension Jacobian are those of the host system with the case's current
+        set, as analyzeCases has them.  It composes with rotor_device and pose_device.  Without it a
+        currentMod > 0 design with a current case raises NotImplementedError; without statics=True it
+        raises ValueError, on an array NotImplementedError.  The default changes nothing."""
+        if line_current and not statics:
+            raise ValueError("analyzeCasesBatch: line_current=True needs statics=True (without it no mooring system "
+                             "is solved: the platform is held at its reference position)")
         if pose_device and not statics:
             raise ValueError("analyzeCasesBatch: pose_device=True needs statics=True (without it every case is solved "
                              "at the reference pose and there is no per-case design)")
@@ -993,7 +1043,8 @@ class Model:
             raise NotImplementedError("analyzeCasesBatch: aero_device=True on an array (analyzeArrayBatch without "
                                       "statics does not evaluate rotors)")
         if statics:
-            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device, pose_device)
+            return self._analyze_cases_statics(cases, tol, want, host, pose_chunk, rotor_device, pose_device,
+                                               line_current)
         if self.nFOWT != 1:
             return self.analyzeArrayBatch(cases, tol=tol, host=host, rotor_device=rotor_device)
         fowt = self.fowtList[0]

@@ -68,12 +68,15 @@ STREAM = re.compile(r"^\s*(buffer_load|global_load)")
 
 def compile_asm(defines=(), csrc=None):
     """Device assembly of every translation unit (compiled in parallel), concatenated.  csrc: the source
-    directory (default: this tree's; tools/asm_same.py passes that of another revision)."""
+    directory (default: this tree's; tools/asm_same.py passes that of another revision, which may lack a
+    unit added since: that unit is left out)."""
     csrc = csrc or G.CSRC
     fd, path = tempfile.mkstemp(suffix=".s")
     os.close(fd)
     procs, parts = [], []
     for unit, flags in G.UNITS:
+        if not os.path.exists(os.path.join(csrc, unit)):
+            continue
         part = path + "." + unit + ".s"
         parts.append(part)
         procs.append(subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags,

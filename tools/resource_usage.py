@@ -1,19 +1,21 @@
 """Per-kernel resource usage of librafthip (VGPR/AGPR/SGPR, spills, scratch, LDS, occupancy)
 from the compiler's -Rpass-analysis=kernel-resource-usage remarks.
-Usage: python tools/resource_usage.py [out.txt]   (compiles rh_abi.hip for gfx950, device only)"""
+Usage: python tools/resource_usage.py [out.txt] [unit.hip]   (compiles one translation unit of csrc for gfx950, device
+only: rh_abi.hip unless named, e.g. rh_moor_current.hip)"""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "raft-teststuff_amd", "csrc", "rh_abi.hip")
+CSRC = os.path.join(ROOT, "raft-teststuff_amd", "csrc")
 KEYS = [("VGPR", "VGPRs"), ("AGPR", "AGPRs"), ("SGPR", "TotalSGPRs"), ("scratch_B", "ScratchSize [bytes/lane]"),
         ("occ_waves_per_SIMD", "Occupancy [waves/SIMD]"), ("VGPR_spill", "VGPRs Spill"),
         ("SGPR_spill", "SGPRs Spill"), ("static_LDS_B", "LDS Size [bytes/block]")]
 
 
 def main():
+    SRC = os.path.join(CSRC, sys.argv[2] if len(sys.argv) > 2 else "rh_abi.hip")
     p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--offload-device-only",
                         "-c", "-o", "/dev/null", SRC, "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True, check=True)
