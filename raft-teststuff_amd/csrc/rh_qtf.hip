@@ -845,8 +845,11 @@ __global__ __launch_bounds__(kQtfTile * NWV) RH_QTF_ATTR void k_qtf_pairs(rh_qtf
           Im = 0.5 * (a2 - d2 - a1 + d1);
           Ip = 0.5 * (a2 + d2 - a1 - d1);
         }
-        // coef / (cosh(k1 R H) cosh(k2 R H)) and Ip / (k1R k2R), hoisted out of the n sum
-        const double cc = k1h * k2h / (ldsd(t1 + 1) * t2[1] * ldsd(t1) * t2[0]);
+        // coef / (cosh(k1 R H) cosh(k2 R H)) and Ip / (k1R k2R), hoisted out of the n sum.  cc is the
+        // product of the two per-frequency factors kayt[6] (as on the MFMA path), not one quotient:
+        // a joint denominator sqrt sqrt cosh cosh would overflow below (k1 + k2) h = 709.78, while
+        // the exponential products above are still finite
+        const double cc = ldsd(t1 + 6) * t2[6];
         const double ipr = Ip / (k1R * k2R);
         const cd c0 = mk(0, rho * g * R * 2 / M_PI / (k1R * k2R));
         cd s = mk(0, 0);
